@@ -1,6 +1,8 @@
 """MS-UNet (Swin-T) training throughput on MI355X: images/sec at 1024^2, bs=8 per GPU.
 
     python bench.py [--gpus N --steps K --warmup W]        # N=1 default; N>1 starts N ranks itself
+    python bench.py ... --full                            # + rooflines, input pipeline, CPU baseline
+    python bench.py ... --dump-outputs DIR                # + the last timed step's results as .npy
     torchrun --nproc-per-node N bench.py --gpus N ...     # one rank per GPU (RCCL), launcher-started
 
 With ``--gpus N > 1`` and no ``WORLD_SIZE`` in the environment, this process touches no GPU: it
@@ -17,14 +19,25 @@ four steps eagerly, times the last two, and replays the captured step as a HIP g
 on when the steadier of them was launch-bound (host issue time >= 0.9 x GPU time), else stays
 eager (MSU_GRAPH=1/0 forces either; the decision falls inside the warmup when W >= 5).  Synthetic StyleGAN2-shaped inputs are generated in HBM before timing
 and copied into the graph's input buffers inside every timed step.  Rank 0 prints ONE
-JSON line.
+JSON line.  A plain run does nothing more: set up, W warmup steps, K timed steps, the line.
 
-Extra objects: ``roofline`` for the dominant kernel (timed live with HIP events on its
+``--dump-outputs DIR`` writes, right after the timed steps, what the last of them handed back:
+``loss.npy`` (the step's return value) and the state it left in the trainer, ``params_<group>.npy``
+and ``exp_avg_<group>.npy`` (master weights and AdamW first moment of the decay / no-decay
+groups), all float32.  A buffer of more than ``DUMP_MAX_ELEMS`` elements is written as a fixed
+seeded sample of that many (sorted indices, seed ``DUMP_SEED``), so the files stay below 64 MB
+in all.  Inputs, initial weights and dropout streams are seeded from the config: equal
+arguments give equal inputs, so two builds can be compared file by file.
+
+``--full`` adds the legs that take runs of their own, after the timed steps (and after the
+dump): ``roofline`` for the dominant kernel (timed live with HIP events on its
 stream), ``roofline_attention`` (window attention), ``roofline_decoder`` (the decoder head
-stack fwd+bwd against the HBM roofline) and ``cpu_baseline`` (the CPU oracle's training step,
-Swin-T and Swin-B, on the box's host cores) and ``input_pipeline`` (the augmentation kernel's
-HBM roofline, and training steps fed from PNG files through the GPU input pipeline: the
-decode- and PCIe-inclusive rate next to the resident one).
+stack fwd+bwd against the HBM roofline), ``cpu_baseline`` (the CPU oracle's training step,
+Swin-T and Swin-B, on the box's host cores), ``dice_vs_ref`` (soft Dice of the HIP path against
+the oracle's) and ``input_pipeline`` (the augmentation kernel's HBM roofline, and training
+steps fed from PNG files through the GPU input pipeline: the decode- and PCIe-inclusive rate
+next to the resident one).  ``--no-roofline``,
+``--no-cpu-baseline`` and ``--no-input-pipeline`` drop single legs of a ``--full`` run.
 """
 import argparse
 import json
@@ -41,6 +54,8 @@ sys.path.insert(0, REPO)
 BACKBONE_NAME = {"swin_t": "Swin-T", "swin_s": "Swin-S", "swin_b": "Swin-B"}
 MFMA_BF16_PEAK_TFLOPS = 2500.0   # MI355X dense bf16 (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_ELEMS = 1 << 22         # per dumped array: 16 MB of float32
+DUMP_SEED = 20240
 
 
 def parse():
@@ -51,10 +66,15 @@ def parse():
     ap.add_argument("--img", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--backbone", default="swin_t")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the rooflines, the input-pipeline leg, the CPU "
+                         "baseline and the Dice comparison (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss and the trainer state it left to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / Dice leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the kernel rooflines")
     ap.add_argument("--no-input-pipeline", action="store_true",
-                    help="skip the PNG -> GpuBatchLoader -> train-step leg (runs after the timed region)")
+                    help="--full without the PNG -> GpuBatchLoader -> train-step leg")
     ap.add_argument("--skip-dead", action="store_true", help="skip the reference's discarded branches (exact)")
     ap.add_argument("--grad-wire", choices=["f32", "bf16", "fp16"], default="f32",
                     help="DP gradient all-reduce precision (BASELINE config 5: fp16 grads)")
@@ -549,6 +569,21 @@ def input_pipeline_leg(device, trainer, batch, img, seed, resident_ms):
     return out
 
 
+def dump_outputs(path, trainer, loss):
+    """``--dump-outputs``: the last timed step's return value and the state it left (float32)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    for name, g in zip(("decay", "no_decay"), trainer.groups):
+        idx = None
+        if g.numel > DUMP_MAX_ELEMS:
+            gen = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, g.numel, (DUMP_MAX_ELEMS,), generator=gen).sort().values.to(g.data.device)
+        for kind, buf in (("params", g.data), ("exp_avg", g.exp_avg)):
+            v = buf if idx is None else buf[idx]
+            np.save(os.path.join(path, f"{kind}_{name}.npy"), v.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -642,15 +677,17 @@ def main():
                        # empty for the product configuration (switches.py)
                        "switches": switches.report()},
         }
-        if not args.no_roofline:
+        if args.dump_outputs and last is not None:
+            dump_outputs(args.dump_outputs, trainer, last)
+        if args.full and not args.no_roofline:
             res["roofline"] = conv_roofline(device, args.batch, args.img, cfg.MODEL.SWIN.EMBED_DIM)
             res["roofline_attention"] = attention_roofline(device, args.batch, args.img, cfg.MODEL.SWIN.EMBED_DIM,
                                                            cfg.MODEL.SWIN.NUM_HEADS[0], cfg.MODEL.ATTN_DROP_RATE)
             res["roofline_decoder"] = decoder_roofline(device, args.batch, args.img, cfg.MODEL.SWIN.EMBED_DIM)
-        if not args.no_input_pipeline and world == 1:
+        if args.full and not args.no_input_pipeline and world == 1:
             res["input_pipeline"] = input_pipeline_leg(device, trainer, args.batch, args.img, cfg.SEED,
                                                        elapsed / args.steps * 1e3)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline()
             res["dice_vs_ref"] = dice_vs_reference(device)
         print(json.dumps(res), flush=True)

@@ -65,7 +65,7 @@ for s in "$@"; do
       cat $O/${TAG}_nt_exp.log ;;
     tests) step tests 1000 python -u -m pytest $R/tests -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider ;;
     smoke) step smoke 300 python -u -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 480 python -u $R/bench.py
+    bench) step bench 480 python -u $R/bench.py --full
            grep '^{' $O/${TAG}_bench.log > $O/${TAG}_bench.json ;;
     # MSU_GRAPH=0: the profiler's per-launch host cost makes the bench's auto policy pick the
     # single-stream graph replay; the profile must show the eager step the bench line measures
@@ -74,7 +74,7 @@ for s in "$@"; do
     # the bench command itself under the profiler (roofline included): the roofline kernel's
     # launches in the trace against the bench line's HIP-event time
     bprof) step bprof 600 rocprofv3 --kernel-trace --stats -d $O/${TAG}_bprof -o p --output-format csv -- \
-             python3 $R/bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-input-pipeline
+             python3 $R/bench.py --steps 10 --warmup 5 --full --no-cpu-baseline --no-input-pipeline
            grep '^{' $O/${TAG}_bprof.log > $O/${TAG}_bprof.json
            python3 $R/tools/roofline_trace.py $O/${TAG}_bprof/p_kernel_trace.csv $O/${TAG}_bprof.json > $O/${TAG}_roofline_trace.txt
            cat $O/${TAG}_roofline_trace.txt ;;

@@ -1,4 +1,4 @@
-"""The bench's roofline launches in a rocprofv3 kernel trace of the bench command: the longest run
+"""The bench's roofline launches in a rocprofv3 kernel trace of ``bench.py --full``: the longest run
 of back-to-back launches of one kernel (conv_roofline: 3 warmup + 10 timed launches of the
 refine2 forward), its average duration over the timed ones, beside the bench line's
 ``roofline.ms_per_launch`` from the same run.
