@@ -334,6 +334,29 @@ int msu_metrics_nblk(long N);
 int msu_seg_metrics(int dtype, const void* logits, const float* label, int B, long N, float threshold,
                     float* part, int nblk, double* out, void* stream);
 
+/* Test-split evaluation with prediction maps (test.py: calculate_metrics and
+ * create_bin_heat_mask_from_list; scripts/map_generator.py save_color_heatmap :23-50,
+ * overlay_mask_on_image :108-141) in one pass: logits [B, 1, H, W] (f32 / bf16 / f16), image
+ * [B, 3, H, W] f32 in [0, 1] or null, label [B, H, W] f32 or null (truth = label > 0);
+ * p = sigmoid(logit).  Every output may be null (not stored):
+ *   prob [B, H, W] f32 = p;  heat [B, H, W] u8 = floor(clamp(p, 0, 1) 255 + 0.5);
+ *   mask [B, H, W] u8 = 255 where p > mask_threshold (M);
+ *   heat_rgb [B, H, W, 3] u8 = floor(v 255 + 0.5), v = clamp((1 - heat_alpha) image + heat_alpha
+ *     lut[min(int(256 p), 255)], 0, 1), lut = matplotlib's 256-entry green / yellow / red table;
+ *   mask_rgb [B, H, W, 3] u8: with u = floor(255 image + 0.5), `color` (0xRRGGBB) on the outline
+ *     (outline != 0: pixels whose 3x3 neighbourhood holds a true and a false M, false outside
+ *     the image), trunc(u (1 - mask_alpha) + color mask_alpha) elsewhere in M, u otherwise;
+ *   sums [B, 12] f64: the msu_seg_metrics columns at sig_threshold, column 11 the
+ *     BCE-with-logits sum.  Without label: sum(p^2), sum(p) and, in column 8, the count of
+ *     p > sig_threshold; the other columns 0.
+ * heat_rgb / mask_rgb need image.  part [B * nblk * 12] f32 scratch (needed with sums), nblk
+ * from msu_pred_maps_nblk.  Deterministic. */
+int msu_pred_maps_nblk(int H, int W);
+int msu_pred_maps(int dtype, const void* logits, const float* image, const float* label, int B, int H, int W,
+                  float sig_threshold, float mask_threshold, float heat_alpha, float mask_alpha, int color,
+                  int outline, float* prob, unsigned char* heat, unsigned char* mask, unsigned char* heat_rgb,
+                  unsigned char* mask_rgb, float* part, double* sums, void* stream);
+
 /* AdamW step (trainer.py:143-152; torch.optim.AdamW, amsgrad=False) over a flat f32
  * parameter range; optional grad unscale (inv_scale) and skip-on-found_inf (GradScaler). */
 int msu_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,

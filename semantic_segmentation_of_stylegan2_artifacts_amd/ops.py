@@ -2029,6 +2029,97 @@ def dynamic_loss(logits, target, alpha, beta, mix):
     return _dynamic_loss(logits, target, float(alpha), float(beta), float(mix))[0]
 
 
+# ----------------------------------------------------------------------------- prediction maps
+# outputs of msunet::prediction_maps, in the order the op returns them (bit k of `want`)
+PRED_OUTPUTS = ("prob", "heat", "mask", "heat_rgb", "mask_rgb", "sums")
+_PRED_NEED_IMAGE = ("heat_rgb", "mask_rgb")
+
+
+def _pred_shapes(logits, want):
+    B, H, W = logits.shape[0], logits.shape[-2], logits.shape[-1]
+    spec = (((B, H, W), torch.float32), ((B, H, W), torch.uint8), ((B, H, W), torch.uint8),
+            ((B, H, W, 3), torch.uint8), ((B, H, W, 3), torch.uint8), ((B, 12), torch.float64))
+    return [(shape if (want >> k) & 1 else (0,), dt) for k, (shape, dt) in enumerate(spec)]
+
+
+def _pred_impl(logits, image, label, sig_threshold, mask_threshold, heat_alpha, mask_alpha, color, outline, want):
+    _need_cuda(logits, image, label)
+    x = logits.contiguous()
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    image = None if image is None else _f32(image)
+    label = None if label is None else _f32(label)
+    outs = [torch.empty(shape, device=x.device, dtype=dt) for shape, dt in _pred_shapes(x, want)]
+    ptr = [_p(t) if t.numel() else None for t in outs]
+    part = None
+    if ptr[5] is not None:
+        nblk = _lib.lib().msu_pred_maps_nblk(H, W)
+        part = torch.empty(B * nblk * 12, device=x.device, dtype=torch.float32)
+    _lib.call("msu_pred_maps", _dt(x), _p(x), _p(image), _p(label), B, H, W, sig_threshold, mask_threshold,
+              heat_alpha, mask_alpha, color, int(outline), ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], _p(part), ptr[5],
+              _s(x))
+    return tuple(outs)
+
+
+def _pred_fake(logits, image, label, sig_threshold, mask_threshold, heat_alpha, mask_alpha, color, outline, want):
+    return tuple(logits.new_empty(shape, dtype=dt) for shape, dt in _pred_shapes(logits, want))
+
+
+def _pred_setup(ctx, inputs, output):
+    ctx.mark_non_differentiable(*output)
+
+
+def _pred_backward(ctx, *grads):
+    return (None,) * 10
+
+
+_prediction_maps = _define(
+    "prediction_maps",
+    "(Tensor logits, Tensor? image, Tensor? label, float sig_threshold, float mask_threshold, float heat_alpha, "
+    "float mask_alpha, int color, bool outline, int want) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+    _pred_impl, _pred_fake, _pred_setup, _pred_backward)
+
+
+def prediction_maps(logits, image=None, label=None, *, sig_threshold=0.5, mask_threshold=0.4, heat_alpha=0.45,
+                    mask_alpha=0.25, color=(255, 0, 255), outline=True, want=None):
+    """Test-split outputs of a batch in one pass (``msu_pred_maps``): logits [B, 1, H, W]
+    (f32 / bf16 / f16), image [B, 3, H, W] in [0, 1] (the model input) and label [B, H, W] or
+    [B, 1, H, W], both optional -> dict of device tensors named in ``want``
+    (``PRED_OUTPUTS``; default: all that the inputs allow): ``prob`` f32 [B, H, W], ``heat`` and
+    ``mask`` u8 [B, H, W], ``heat_rgb`` and ``mask_rgb`` u8 [B, H, W, 3] (need ``image``),
+    ``sums`` f64 [B, 12] (``validation.COLS`` + the BCE sum; see include/msunet_hip.h).
+    No autograd."""
+    if want is None:
+        want = tuple(k for k in PRED_OUTPUTS if image is not None or k not in _PRED_NEED_IMAGE)
+    unknown = [k for k in want if k not in PRED_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown prediction_maps outputs {unknown} (known: {PRED_OUTPUTS})")
+    if logits.dim() != 4 or logits.shape[1] != 1:
+        raise ValueError(f"Binary task expected logits [B, 1, H, W], got {tuple(logits.shape)}")
+    B, _, H, W = logits.shape
+    if image is None and any(k in _PRED_NEED_IMAGE for k in want):
+        raise ValueError("heat_rgb / mask_rgb need the image")
+    if image is not None:
+        if image.shape[0] != B:
+            raise ValueError(f"batch mismatch: logits {B}, image {image.shape[0]}")
+        if tuple(image.shape[1:]) != (3, H, W):
+            raise ValueError(f"image size {tuple(image.shape)} does not match logits {tuple(logits.shape)}")
+    if label is not None:
+        if label.shape[0] != B:
+            raise ValueError(f"batch mismatch: logits {B}, labels {label.shape[0]}")
+        if label[0].numel() != H * W:
+            raise ValueError(f"label size {tuple(label.shape)} does not match logits {tuple(logits.shape)}")
+    _need_cuda(logits, image, label)
+    if logits.dtype not in _DT:
+        logits = logits.float()
+    r, g, b = (int(c) for c in color)
+    if not all(0 <= c <= 255 for c in (r, g, b)):
+        raise ValueError(f"color must be three bytes, got {tuple(color)}")
+    bits = sum(1 << PRED_OUTPUTS.index(k) for k in set(want))
+    outs = _prediction_maps(logits, image, label, float(sig_threshold), float(mask_threshold), float(heat_alpha),
+                            float(mask_alpha), (r << 16) | (g << 8) | b, bool(outline), bits)
+    return {k: outs[PRED_OUTPUTS.index(k)] for k in PRED_OUTPUTS if k in want}
+
+
 # ----------------------------------------------------------------------------- optimizer
 def adamw_(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
            inv_scale=None, found_inf=None):
