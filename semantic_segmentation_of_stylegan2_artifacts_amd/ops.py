@@ -16,6 +16,7 @@ modules in ``network/`` call.  They cast the activation to the autocast dtype an
 registered op.  (A plain ``autograd.Function`` route around the dispatcher measured equal on
 the GPU-bound 1024^2 step, r02c 50.50 vs 50.57 ms: gone.)
 """
+import contextlib
 import ctypes
 import functools
 
@@ -142,9 +143,6 @@ def join_side_streams():
         torch.cuda.current_stream(idx).wait_stream(st)
 
 
-_join_queued = False
-
-
 def _guard_side_write(p, ev):
     """p.grad was just updated on the side stream (event ev).  If autograd later accumulates
     another gradient into p on the main stream (e.g. the qkv bias: its Linear adds db here,
@@ -165,6 +163,17 @@ def _guard_side_write(p, ev):
         p._msu_side_hooked = True
 
 
+# ----------------------------------------------------------------------------- per-backward state
+# What one backward node parks for a later node or for the end of its backward: the five
+# containers below and the id of the backward that owns them (_bwd_task).  Every writer calls
+# _join_at_end_of_backward() BEFORE it parks anything: the first call of a backward queues
+# _end_of_backward on the autograd engine, which flushes, joins and resets.  The engine drops
+# its queued callbacks when a node raises, so the owner is remembered by its graph-task id and
+# not by a flag: state found under another id is what a failed backward left, and is discarded
+# (reset_backward_state) before the new backward parks its own.  A nested (reentrant) backward
+# would look like a new owner to its outer one and is not supported; the model's checkpointing
+# is use_reentrant=False, which runs none.
+#
 # Tensors a side-stream kernel is still reading.  record_stream only keeps their memory from
 # being reused; it does not stop autograd from accumulating into them IN PLACE: a gradient
 # returned for two inputs (the add-LN backward hands the same `da` to the residual and to the
@@ -175,6 +184,10 @@ _side_keep = []
 # parameters whose _msu_side_event was set in this backward: cleared at its end, so no later
 # wait (a hook, _linbwd) orders on an event of an earlier step or from outside a capture
 _side_event_params = []
+# deferred LayerNorm partials waiting for their batched reduction (see _LN_DEFER below)
+_ln_pending = []  # (part, nparts, C, gamma, beta)
+_bwd_task = -1  # torch's graph-task id of the backward whose end is queued; -1: none
+backward_discards = 0  # times a failed backward's leftovers were discarded (tests)
 
 
 # Residual-gradient handoff.  A Swin block whose input x is a plain tensor (a stage's first
@@ -210,11 +223,13 @@ def _park(key, g):
     """A reader's gradient of the keyed tensor, handed to the adder; False when there is no key
     or the adder already ran (the caller returns g to autograd)."""
     global res_parked
-    if not key or key in _res_closed:
+    if not key:
+        return False
+    _join_at_end_of_backward()  # clears the mailbox at the end of this backward
+    if key in _res_closed:
         return False
     _res_handoff.setdefault(key, []).append(g)
     res_parked += 1
-    _join_at_end_of_backward()  # clears the mailbox at the end of this backward
     return True
 
 
@@ -222,32 +237,80 @@ def _take(key):
     """The adder's side: the parked gradients of key (and the key closed)."""
     if not key:
         return []
-    _res_closed.add(key)
     _join_at_end_of_backward()
+    _res_closed.add(key)
     return _res_handoff.pop(key, [])
 
 
-def _end_of_backward():
-    global _join_queued, res_dropped
-    _join_queued = False
-    _flush_ln()
-    res_dropped += sum(len(v) for v in _res_handoff.values())
+def reset_backward_state():
+    """Drop everything a backward parked, unflushed and unjoined: pending LayerNorm partials,
+    the handoff mailbox and its closed keys, the side-stream keep list and event guards; the
+    next backward queues its own end-of-backward callback.  For a caller that caught an
+    exception out of ``backward()`` (the engine ran no callback); a no-op with nothing parked."""
+    global _bwd_task
+    _ln_pending.clear()
     _res_handoff.clear()
     _res_closed.clear()
-    join_side_streams()
-    _side_keep.clear()  # the main stream now waits for every side-stream read
+    _side_keep.clear()
     for p in _side_event_params:
         p._msu_side_event = None
     _side_event_params.clear()
+    _bwd_task = -1
+
+
+def _end_of_backward():
+    global res_dropped
+    _flush_ln()
+    res_dropped += sum(len(v) for v in _res_handoff.values())
+    join_side_streams()  # the main stream now waits for every side-stream read and .grad write
+    reset_backward_state()
 
 
 def _join_at_end_of_backward():
-    """Once per backward pass: when it ends, the main stream waits for the side stream, so
-    .grad read after ``backward()`` returns is complete (overlap stays inside backward)."""
-    global _join_queued
-    if not _join_queued:
-        torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
-        _join_queued = True
+    """The first call of a backward pass queues its end: the pending LayerNorm partials are
+    summed and the main stream waits for the side stream, so .grad read after ``backward()``
+    returns is complete (overlap stays inside backward).  State of another backward still here
+    (it raised) is discarded first."""
+    global _bwd_task, backward_discards
+    task = torch._C._current_graph_task_id()
+    if task == _bwd_task and task != -1:
+        return
+    if _bwd_task != -1:
+        backward_discards += 1
+        reset_backward_state()
+    torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)  # raises outside backward
+    _bwd_task = task
+
+
+@contextlib.contextmanager
+def _on_side(device, reads=(), writes=()):
+    """A backward node's work on the side stream: inside the ``with`` the current stream is the
+    side stream, forked from the main stream at the point of entry.  ``reads``: the tensors the
+    work reads that the main stream produced (what it allocates inside is the side stream's
+    own); ``writes``: the direct parameters whose .grad it adds into (None entries skipped).
+    The one place that knows the protocol, each step against one hazard:
+    * side waits for main -- the reads are complete;
+    * the end-of-backward join is queued -- .grad is complete when ``backward()`` returns;
+    * record_stream per read -- the main stream does not reuse its memory meanwhile;
+    * one reference per read in _side_keep -- autograd does not accumulate into it in place;
+    * a fresh event after the work, left on every written parameter (_guard_side_write) -- a
+      later main-stream writer of the same .grad (autograd's accumulation, _linbwd) waits for
+      it; a fresh one per section, so a graph capture turns each record / wait pair into an edge;
+    * the gradient bucketer hears of the parameters last, after the event."""
+    side = _side_stream_for(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    _join_at_end_of_backward()
+    for t in reads:
+        t.record_stream(side)
+        _side_keep.append(t)
+    with torch.cuda.stream(side):
+        yield
+    ev = torch.cuda.Event()
+    ev.record(side)
+    for p in writes:
+        if p is not None:
+            _guard_side_write(p, ev)
+    _notify(*writes)
 
 
 def _direct(*params):
@@ -300,7 +363,6 @@ def _ln_grads(ctx, C, device):
 # (last-arriving blocks summing ~1 MB of partials, 8-15 us at the end of every launch, r06ac)
 # leaves its critical path; the parameters are notified to the gradient bucketer after the batch.
 _LN_DEFER = switches.on("MSU_LN_DEFER")
-_ln_pending = []  # (part, nparts, C, gamma, beta)
 ln_batches = 0  # batched reductions launched (tests)
 
 
@@ -336,10 +398,14 @@ def _ln_finish(ctx, part, n, C):
     if not ctx.ln_deferred:
         _notify(w, b)
         return
+    _join_at_end_of_backward()
     if _ln_pending and _ln_pending[-1][2] != C:
         _flush_ln()
+    elif any(e[3] is w or e[4] is b for e in _ln_pending):
+        # a LayerNorm used twice in one forward: two blocks of one batched launch would
+        # read-add-write the same .grad rows; the first share goes in alone
+        _flush_ln()
     _ln_pending.append((part, n, C, w, b))
-    _join_at_end_of_backward()
 
 
 def _ln_parts(rows, C, device):
@@ -707,27 +773,14 @@ def _attn_backward(ctx, dout, _dkeep, _dws=None):
         # Linear's db: on the side stream too when that Linear runs the two-kernel backward
         # (one stream, program order), or on the main stream in the one-pass backward
         # (_linbwd, stage 0), which runs later in this backward and first makes the main
-        # stream wait on the event recorded below (bias._msu_side_event)
-        # (the fork is a fresh torch event per call: a HIP graph capture of the step turns
-        # every record / wait pair into its own edge)
-        main = torch.cuda.current_stream(qkv.device)
-        side = _side_stream_for(qkv.device)
+        # stream wait on the event the section leaves on the bias (bias._msu_side_event)
         _lib.call("msu_win_attn_bwd2", _dt(qkv), _p(qkv), _p(qkv_bias), tbl, _p(dout), _p(dqkv),
                   None, None, _p(ws), B, H, W, C, nh, shift, p_drop, seed, _p(seed_dev), kp,
-                  main.cuda_stream, -1)
-        side.wait_stream(main)
-        ws.record_stream(side)
-        _side_keep.append(ws)
-        with torch.cuda.stream(side):
+                  _s(qkv), -1)
+        with _on_side(qkv.device, reads=(ws,), writes=(bp, tp)):  # forks after the kernel above
             # the reductions add straight into .grad (no .grad adds behind them)
             _lib.call("msu_win_attn_bwd_tail2", _dt(qkv), _p(ws), _p(tp.grad), _p(bp.grad), B, H, W, C, nh, 1,
-                      side.cuda_stream)
-        ev = torch.cuda.Event()
-        ev.record(side)
-        _guard_side_write(bp, ev)
-        _guard_side_write(tp, ev)
-        _join_at_end_of_backward()
-        _notify(bp, tp)
+                      _s(qkv))
         return dqkv, None, None, None, None, None, None, None
     dtable = torch.empty_like(table)
     dbias = torch.empty(3 * C, device=qkv.device, dtype=torch.float32)
@@ -911,8 +964,6 @@ def tok_supported_epi(M, N, K, epi):
     return r
 
 
-
-
 def tok_gemm(a, w, bias=None, epi=TOK_PLAIN, h=None, a2=None, gelu_only=False):
     """16-bit Y = epi(A . W^T + bias) on the token GEMM kernel.  a: [..., K1] (+ a2: [..., K-K1]),
     w: [N, K] (a's dtype), bias: [N] f32.  Returns Y (and GELU(Y) for TOK_GELU_DUAL).
@@ -979,58 +1030,45 @@ def _gemm_dx(dy, w, epi=TOK_PLAIN, h=None, param=None):
 
 
 def _gelu16(h):
-    """GELU(h) in h's 16-bit format on the current stream (msu_gelu_fwd: the fused epilogues'
-    arithmetic and rounding)."""
+    """GELU(h) in h's format (16-bit, or f32) on the current stream (msu_gelu_fwd: the fused
+    epilogues' arithmetic and rounding)."""
     g = torch.empty_like(h)
     _lib.call("msu_gelu_fwd", _dt(h), _p(h), _p(g), h.numel(), _s(h))
     return g
 
 
-def _wgrad(dy, x, weight, bias, M, N, K, x_gelu_of=None, side_ok=True):
-    """Linear weight/bias gradients on msu_linear_wgrad; (None, None) when accumulated
-    straight into the trainer's flat .grad views.  x None: x = GELU(x_gelu_of), derived on the
-    stream the weight gradient runs on.  side_ok False: on the main stream even with direct
-    parameters (a Linear whose input needs no gradient -- PatchEmbed's, the last node of backward:
-    nothing is left on the main stream to overlap it, and behind the side stream's queue it would
-    only delay the end-of-backward join)."""
-    L = _lib.lib()
-    if _direct(weight) and (bias is None or _direct(bias)):
-        if _side_enabled and _side_wgrad and side_ok:
-            src = x if x is not None else x_gelu_of
-            main = torch.cuda.current_stream(src.device)
-            side = _side_stream_for(src.device)
-            side.wait_stream(main)  # dy and x are ready
-            with torch.cuda.stream(side):
-                if x is None:
-                    x = _gelu16(x_gelu_of)  # allocated on the side stream, used there only
-                ws = torch.empty(L.msu_wgrad_workspace(M, N, K), device=x.device, dtype=torch.float32)
-                _lib.call("msu_linear_wgrad", _dt(x), _p(dy), _p(x), _p(weight.grad),
-                          _p(None if bias is None else bias.grad), _p(ws), M, N, K, 1, side.cuda_stream)
-            dy.record_stream(side)  # their memory is not reused by the main stream meanwhile
-            src.record_stream(side)
-            _side_keep.append(dy)  # ... nor accumulated into in place (see _side_keep)
-            _side_keep.append(src)
-            ev = torch.cuda.Event()
-            ev.record(side)
-            _guard_side_write(weight, ev)
-            if bias is not None:
-                _guard_side_write(bias, ev)
-            _join_at_end_of_backward()
-        else:
-            if x is None:
-                x = _gelu16(x_gelu_of)
-            ws = torch.empty(L.msu_wgrad_workspace(M, N, K), device=x.device, dtype=torch.float32)
-            _lib.call("msu_linear_wgrad", _dt(x), _p(dy), _p(x), _p(weight.grad),
-                      _p(None if bias is None else bias.grad), _p(ws), M, N, K, 1, _s(x))
-        _notify(weight, bias)
-        return None, None
+def _wgrad_launch(dy, x, dw, db, M, N, K, acc, x_gelu_of=None):
+    """The one launcher of the Linear weight-gradient kernel, on the current stream: dw [N, K]
+    (+ db [N], or None) = dy^T . x, added into them when acc = 1.  dw may be a column slice of
+    a wider [N, Kt] gradient (its row stride is the kernel's ldw; a whole gradient: ldw = K,
+    msu_linear_wgrad).  x None: x = GELU(x_gelu_of), derived here -- on the stream, and from the
+    memory pool, the weight gradient runs on -- as is the workspace."""
     if x is None:
         x = _gelu16(x_gelu_of)
-    ws = torch.empty(L.msu_wgrad_workspace(M, N, K), device=x.device, dtype=torch.float32)
-    dw = torch.empty(N, K, device=x.device, dtype=torch.float32)
-    db = torch.empty(N, device=x.device, dtype=torch.float32) if bias is not None else None
-    _lib.call("msu_linear_wgrad", _dt(x), _p(dy), _p(x), _p(dw), _p(db), _p(ws), M, N, K, 0, _s(x))
-    return dw, db
+    ws = torch.empty(_lib.lib().msu_wgrad_workspace(M, N, K), device=x.device, dtype=torch.float32)
+    _lib.call("msu_linear_wgrad_ld", _dt(x), _p(dy), _p(x), _p(dw), dw.stride(0), _p(db), _p(ws), M, N, K, acc,
+              _s(x))
+
+
+def _wgrad(dy, x, weight, bias, M, N, K, x_gelu_of=None, side_ok=True):
+    """Linear weight/bias gradients; (None, None) when accumulated straight into the trainer's
+    flat .grad views.  x None: x = GELU(x_gelu_of), derived on the stream the weight gradient
+    runs on.  side_ok False: on the main stream even with direct parameters (a Linear whose input
+    needs no gradient -- PatchEmbed's, the last node of backward: nothing is left on the main
+    stream to overlap it, and behind the side stream's queue it would only delay the
+    end-of-backward join)."""
+    src = x if x is not None else x_gelu_of
+    if not (_direct(weight) and (bias is None or _direct(bias))):
+        dw = torch.empty(N, K, device=src.device, dtype=torch.float32)
+        db = torch.empty(N, device=src.device, dtype=torch.float32) if bias is not None else None
+        _wgrad_launch(dy, x, dw, db, M, N, K, 0, x_gelu_of)
+        return dw, db
+    side = _side_enabled and _side_wgrad and side_ok
+    with _on_side(src.device, (dy, src), (weight, bias)) if side else contextlib.nullcontext():
+        _wgrad_launch(dy, x, weight.grad, None if bias is None else bias.grad, M, N, K, 1, x_gelu_of)
+    if not side:
+        _notify(weight, bias)
+    return None, None
 
 
 def _shadow(param, dt):
@@ -1113,9 +1151,30 @@ def _gemm(a, w, bias=None, epi=TOK_PLAIN, h=None, gelu_only=False):
         return torch.nn.functional.linear(a, w, None if bias is None else bias.to(a.dtype))
 
 
-def _mm(a, w, bias=None):
-    """16-bit a . w^T (+ bias) on the routed GEMM."""
-    return _gemm(a, w, bias)
+def _linear_fwd(x, weight, bias, epi=TOK_PLAIN):
+    """epi(x . W^T + b) in x's dtype from the f32 master weight / bias: 16-bit on the routed HIP
+    GEMM when one covers the shape, else the library matmul with autocast off.  TOK_GELU_DUAL
+    (no bias): the pair (Y, GELU(Y))."""
+    w = _shadow(weight, x.dtype)
+    N, K = w.shape
+    M = x.numel() // K
+    if x.dtype in _LOW and gemm_route(M, N, K, epi) != "lib":
+        if epi == TOK_GELU_DUAL:
+            return _gemm(x, w, _zero_bias(N, x.device), epi)  # the dual epilogue needs a bias
+        return _gemm(x, w, None if bias is None else _f32(bias))
+    with torch.autocast("cuda", enabled=False):
+        y = torch.nn.functional.linear(x, w, None if bias is None else _shadow(bias, x.dtype))
+    return (y, _gelu16(y)) if epi == TOK_GELU_DUAL else y
+
+
+def _linear_dx(dy, w, weight):
+    """dy . w, the input gradient of a Linear (w: the 16-bit / f32 form of ``weight`` the
+    forward used): the routed HIP GEMM or, as in the forward, the library matmul."""
+    N, K = w.shape
+    if dy.dtype in _LOW and gemm_route(dy.numel() // N, K, N) != "lib":
+        return _gemm_dx(dy, w, param=weight)
+    with torch.autocast("cuda", enabled=False):
+        return dy.matmul(w)
 
 
 # ----------------------------------------------------------------------------- Linear
@@ -1123,15 +1182,7 @@ def _linear_impl(x, weight, bias, handoff=0):
     """Y = x . W^T + b in x's dtype; the f32 master weight / bias are cast inside the op so
     that the parameter gradients are the f32 ones of the weight-gradient kernel."""
     _need_cuda(x)
-    dt = x.dtype
-    w = _shadow(weight, dt)
-    N, K = w.shape
-    M = x.numel() // K
-    if dt in _LOW and gemm_route(M, N, K) != "lib":
-        return _gemm(x, w, None if bias is None else _f32(bias))
-    b = None if bias is None else _shadow(bias, dt)
-    with torch.autocast("cuda", enabled=False):
-        return torch.nn.functional.linear(x, w, b)
+    return _linear_fwd(x, weight, bias)
 
 
 def _linear_fake(x, weight, bias, handoff=0):
@@ -1202,13 +1253,7 @@ def _linear_grads(ctx, dy):
         dx = _linbwd(dy.contiguous(), x, weight, bias, M, N, K)
         if dx is not None:
             return (None if _park(key, dx) else dx), None, None
-    dx = None
-    if ctx.needs_input_grad[0]:
-        if x.dtype in _LOW and gemm_route(M, K, N) != "lib":
-            dx = _gemm_dx(dy, w, param=weight)
-        else:
-            with torch.autocast("cuda", enabled=False):
-                dx = dy.matmul(w)
+    dx = _linear_dx(dy, w, weight) if ctx.needs_input_grad[0] else None
     if dx is not None and _park(key, dx):
         dx = None  # x's gradient goes to its keyed LayerNorm's backward kernel
     if not (ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])):
@@ -1281,17 +1326,6 @@ def _linear_cat_setup(ctx, inputs, output):
     ctx.handoff = inputs[4] if len(inputs) > 4 else 0
 
 
-def _wgrad_into(dy, x, dw, db, M, N, K, acc):
-    """msu_linear_wgrad of one input half: dw [N, K] may be a column slice of a wider [N, Kt]
-    gradient (row stride Kt, the kernel's ldw); acc = 1 adds into it."""
-    L = _lib.lib()
-    ws = torch.empty(L.msu_wgrad_workspace(M, N, K), device=x.device, dtype=torch.float32)
-    _lib.call("msu_linear_wgrad_ld", _dt(x), _p(dy), _p(x), _p(dw), dw.stride(0), _p(db), _p(ws), M, N, K, acc,
-              _s(x))
-
-
-
-
 def _linear_cat_backward(ctx, dy):
     x, skip = ctx.saved_tensors
     weight, bias = ctx.params
@@ -1309,38 +1343,24 @@ def _linear_cat_backward(ctx, dy):
     # weight gradient per half straight into the column slices of dW (bias with the first):
     # the trainer's flat .grad (accumulate) or a fresh [N, C1 + C2] gradient
     direct = _direct(weight, bias)
-    if direct and _side_enabled and _side_wgrad:
-        # on the weight-gradient side stream like every other Linear's (the shared skip-fusion
-        # Linears -- concat_back_dim[2 / 3] serve the central decoders too -- then have all
-        # their .grad writers on one stream, in program order)
-        main = torch.cuda.current_stream(x.device)
-        side = _side_stream_for(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            _wgrad_into(dy, x, weight.grad[:, :C1], bias.grad, M, N, C1, 1)
-            _wgrad_into(dy, skip, weight.grad[:, C1:], None, M, N, C2, 1)
-        for t in (dy, x, skip):
-            t.record_stream(side)
-            _side_keep.append(t)
-        ev = torch.cuda.Event()
-        ev.record(side)
-        _guard_side_write(weight, ev)
-        _guard_side_write(bias, ev)
-        _join_at_end_of_backward()
-        _notify(weight, bias)
-        return outs[0], outs[1], None, None, None
     if direct:
         dw, db, acc = weight.grad, bias.grad, 1
     else:
         dw = torch.empty(N, C1 + C2, device=x.device, dtype=torch.float32)
         db = torch.empty(N, device=x.device, dtype=torch.float32)
         acc = 0
-    _wgrad_into(dy, x, dw[:, :C1], db, M, N, C1, acc)
-    _wgrad_into(dy, skip, dw[:, C1:], None, M, N, C2, acc)
-    if direct:
+    # on the weight-gradient side stream like every other Linear's (the shared skip-fusion
+    # Linears -- concat_back_dim[2 / 3] serve the central decoders too -- then have all their
+    # .grad writers on one stream, in program order)
+    side = direct and _side_enabled and _side_wgrad
+    with _on_side(x.device, (dy, x, skip), (weight, bias)) if side else contextlib.nullcontext():
+        _wgrad_launch(dy, x, dw[:, :C1], db, M, N, C1, acc)
+        _wgrad_launch(dy, skip, dw[:, C1:], None, M, N, C2, acc)
+    if not direct:
+        return outs[0], outs[1], dw, db, None
+    if not side:
         _notify(weight, bias)
-        return outs[0], outs[1], None, None, None
-    return outs[0], outs[1], dw, db, None
+    return outs[0], outs[1], None, None, None
 
 
 _linear_cat = _define("linear_cat", "(Tensor x, Tensor skip, Tensor weight, Tensor bias, int handoff=0) -> Tensor",
@@ -1698,20 +1718,8 @@ def _conv_wgrad_param(a, dz, mode, B, H, W, Cin, Cout, weight, bias):
     them: off the activation-gradient chain, 2 x 1.3 ms per step on the main stream before)."""
     if not (_CONV_SIDE and _side_enabled and _direct(weight, bias)):
         return _conv_wgrad(a, dz, mode, B, H, W, Cin, Cout)
-    main = torch.cuda.current_stream(a.device)
-    side = _side_stream_for(a.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
+    with _on_side(a.device, reads=(a, dz), writes=(weight, bias)):
         _conv_wgrad(a, dz, mode, B, H, W, Cin, Cout, into=(weight, bias))
-    for t in (a, dz):
-        t.record_stream(side)
-        _side_keep.append(t)
-    ev = torch.cuda.Event()
-    ev.record(side)
-    _guard_side_write(weight, ev)
-    _guard_side_write(bias, ev)
-    _notify(weight, bias)
-    _join_at_end_of_backward()
     return None, None
 
 
@@ -1864,17 +1872,7 @@ def _linear_gelu_impl(x, weight):
     (FinalPatchExpand_X4_V2.expand -> act, model_parts.py:458-460); the activation gradient is
     applied by the consumer (refine_conv_act's dgrad epilogue)."""
     _need_cuda(x)
-    dt = x.dtype
-    w = _shadow(weight, dt)
-    N, K = w.shape
-    M = x.numel() // K
-    if dt in _LOW and gemm_route(M, N, K, TOK_GELU_DUAL) != "lib":
-        return _gemm(x, w, _zero_bias(N, x.device), TOK_GELU_DUAL)
-    with torch.autocast("cuda", enabled=False):
-        y = torch.nn.functional.linear(x, w)
-    g = torch.empty_like(y)
-    _lib.call("msu_gelu_fwd", _dt(y), _p(y), _p(g), y.numel(), _s(y))
-    return y, g
+    return _linear_fwd(x, weight, None, TOK_GELU_DUAL)
 
 
 def _linear_gelu_fake(x, weight):
@@ -1899,13 +1897,7 @@ def _linear_gelu_backward(ctx, dy, _dg):
     dy = _as(dy, x.dtype)
     N, K = w.shape
     M = dy.numel() // N
-    dx = None
-    if ctx.needs_input_grad[0]:
-        if x.dtype in _LOW and gemm_route(M, K, N) != "lib":
-            dx = _gemm_dx(dy, w, param=weight)
-        else:
-            with torch.autocast("cuda", enabled=False):
-                dx = dy.matmul(w)
+    dx = _linear_dx(dy, w, weight) if ctx.needs_input_grad[0] else None
     dw, _ = _wgrad(dy, x, weight, None, M, N, K)
     return dx, dw
 

@@ -672,7 +672,7 @@ class Trainer:
             # handles in the reducer: a later eager step must start from a clean bucket state
             if self.reducer is not None:
                 self.reducer.reset()
-            ops._side_keep.clear()
+            ops.reset_backward_state()  # the engine ran no end-of-backward callback
             self._sx = self._sy = None
             torch.cuda.synchronize(self.device)
             if self.world_size > 1:

@@ -6,7 +6,9 @@ the plain autograd gradients bitwise -- the same partials summed in the same ord
   the four LayerNorm forms of the path (torchvision block norms, the fused residual + norm,
   PatchMerging's gather + norm, PatchExpand's rearrange + norm; model_parts.py:87-94, :403-405);
 * the refine convs' weight / bias gradients added into ``.grad`` on the side stream
-  (ops._conv_wgrad_param; model_parts.py:447-448, :468-471)."""
+  (ops._conv_wgrad_param; model_parts.py:447-448, :468-471);
+* the deferred LayerNorm reduction with one gamma / beta pair used twice in a forward, and after a
+  backward that raised and left its partials parked (the failed-backward rule)."""
 import pytest
 import torch
 
@@ -107,3 +109,74 @@ def test_refine_conv_param_grads_on_side_stream_equal_autograd(d2s):
         res[direct] = (xg.grad.clone(), w.grad.clone(), b.grad.clone())
     for name, u, r in zip(("dx", "dw", "db"), res[True], res[False]):
         assert torch.equal(u, r), name
+
+
+def _ln_arms(ops, fwd, x, C=96):
+    """(dx, dgamma, dbeta) of ``fwd(x, w, b)`` under bf16 autocast for fresh parameters (zeroed
+    .grad), keyed by ``direct``: False is the autograd arm, the reference of the direct one."""
+    res = {}
+    for direct in (False, True):
+        w, b = _params(C, 9, direct)
+        xg = x.clone().requires_grad_(True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = fwd(xg, w, b)
+        dy = torch.randn(y.shape, generator=torch.Generator().manual_seed(5)).to(DEV, y.dtype)
+        y.backward(dy)
+        ops.join_side_streams()
+        torch.cuda.synchronize()
+        res[direct] = (xg.grad.clone(), w.grad.clone(), b.grad.clone())
+    return res
+
+
+def _assert_deferred_equal(res):
+    for name, a, r in zip(("dx", "dgamma", "dbeta"), res[True], res[False]):
+        if name == "dx":
+            assert torch.equal(a, r), name
+        else:
+            assert ((a - r).norm() / r.norm()).item() <= 1e-6, name
+
+
+def test_ln_pair_used_twice_in_one_forward(monkeypatch):
+    """One gamma / beta pair behind two LayerNorms of one forward: the second backward's partials
+    do not join the first's in one batched reduction (two blocks of one launch would read-add-
+    write the same .grad rows) -- the first share is flushed alone, two launches in all."""
+    ops = _ops()
+    monkeypatch.setattr(ops, "_LN_DEFER", True)
+    batches = ops.ln_batches
+    x = torch.randn(2, 32, 32, 96, generator=torch.Generator().manual_seed(3)).to(DEV, torch.bfloat16)
+    res = _ln_arms(ops, lambda xg, w, b: ops.layer_norm(ops.layer_norm(xg, w, b), w, b), x)
+    assert ops.ln_batches - batches == 2
+    assert not ops._ln_pending
+    _assert_deferred_equal(res)
+
+
+class _RaiseInBackward(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        raise RuntimeError("backward node failed")
+
+
+def test_good_step_after_a_raising_backward(monkeypatch):
+    """A backward that raises after a deferred LayerNorm backward leaves that node's partials
+    parked (the engine runs no end-of-backward callback).  The next backward discards them: its
+    gradients hold none of the failed pass's partials and miss none of their own."""
+    ops = _ops()
+    monkeypatch.setattr(ops, "_LN_DEFER", True)
+    x = torch.randn(2, 32, 32, 96, generator=torch.Generator().manual_seed(3)).to(DEV, torch.bfloat16)
+    w, b = _params(96, 9, True)
+    xg = x.clone().requires_grad_(True)
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        y = ops.layer_norm(_RaiseInBackward.apply(xg), w, b)  # the LayerNorm's backward runs first
+    with pytest.raises(RuntimeError, match="backward node failed"):
+        y.backward(torch.ones_like(y))
+    assert len(ops._ln_pending) == 1  # what the failed backward left
+    batches, discards = ops.ln_batches, ops.backward_discards
+    res = _ln_arms(ops, lambda xg, w, b: ops.layer_norm(xg, w, b), x)
+    assert ops.ln_batches - batches == 1 and ops.backward_discards - discards == 1
+    assert not ops._ln_pending and not ops._side_keep
+    _assert_deferred_equal(res)
+    assert not w.grad.any() and not b.grad.any()  # the failed pass's partials went nowhere

@@ -46,7 +46,7 @@ for s in "$@"; do
       python3 $R/tools/ab_table.py $O/${TAG}_nt_a3.log F0A0 F0A1
       step nt_a3_tests 600 $PYT -m gpu $R/tests/test_gpu_nt_gemm.py ;;
     nt_dyn)
-      # NT GEMM kernel times per shape: the tile queue (default) vs MSU_NT_DYN=0, interleaved twice
+      # NT GEMM kernel times per shape: the tile queue (opt-in, MSU_NT_DYN=1) vs MSU_NT_DYN=0, interleaved twice
       for E in 1 0 1 0; do
         MSU_NT_DYN=$E timeout -k 10 200 python -u $R/tools/nt_shapes.py 20 dyn$E >> $O/${TAG}_nt_dyn.log 2>&1 || exit 3
       done
