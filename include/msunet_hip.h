@@ -262,14 +262,16 @@ int msu_nt_gemm_kn(int dtype, const void* A, const void* Wk, const float* bias, 
 
 /* ---------------------------------------------------------------- streaming ops
  * nn.GELU() (exact erf): torchvision MLP activation, FinalPatchExpand_X4_V2.act. */
-/* Stage-0 Swin MLP forward, fused (csrc/mlp_fused.hip; replaces mlp.0 -> GELU -> mlp.3 of
- * torchvision's block, model_parts.py:538): y = W2 GELU(W1 x + b1) + b2 with the hidden
- * activation kept on chip; h (nullable) receives the 16-bit pre-activation W1 x + b1 [M][384]
+/* Swin MLP forward, fused (csrc/mlp_fused.hip, csrc/mlp_s1.hip; replaces mlp.0 -> GELU -> mlp.3
+ * of torchvision's block, model_parts.py:538): y = W2 GELU(W1 x + b1) + b2 with the hidden
+ * activation kept on chip; h (nullable) receives the 16-bit pre-activation W1 x + b1 [M][Hd]
  * for the backward (training; null on the no-grad path: the reference's discarded branches
- * layers_cent1[-1] / layers_cent2[-1], model_parts.py:795 / :807, and evaluation).  x, y [M][96],
- * w1 [384][96], w2 [96][384] in the 16-bit format dtype, b1 / b2 f32, all 16-B aligned.
- * msu_mlp_fused_supported(C, Hd): 1 for C = 96, Hd = 384.  Returns 0, -2 (unsupported).
- * The backward's mlp.3 step is msu_linear_bwd with X = null and H = h. */
+ * layers_cent1[-1] / layers_cent2[-1], model_parts.py:795 / :807, and evaluation).  x, y [M][C],
+ * w1 [Hd][C], w2 [C][Hd] in the 16-bit format dtype, b1 / b2 f32, all 16-B aligned.
+ * msu_mlp_fused_supported(C, Hd): 1 for (C, Hd) = (96, 384) (Swin-T/S stage 0, weights resident
+ * in LDS), (192, 768) (Swin-T/S stage 1) and (128, 512) (Swin-B stage 0; both with the weights
+ * streamed through an LDS ring).  Returns 0, -2 (unsupported).
+ * The backward's mlp.3 step at (96, 384) is msu_linear_bwd with X = null and H = h. */
 int msu_mlp_fused_supported(int C, int Hd);
 /* No-grad second half of a stage-0 block: s_out = a + bscale[sample] * br (16-bit; bscale null = 1,
  * rows_per_sample rows per sample), y = mlp(LN(s) with gamma / beta / eps) -- the residual-add

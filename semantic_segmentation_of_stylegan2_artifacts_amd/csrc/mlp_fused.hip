@@ -302,20 +302,25 @@ int launch_mlp(const MlpArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// mlp_s1.hip: the stage-1 form (C = 192, hidden 768, weights streamed through an LDS ring)
+// mlp_s1.hip: the streamed-weight form (weights through an LDS ring; hidden 4 C) and its widths
+// (C = 192: Swin-T/S stage 1; C = 128: Swin-B stage 0)
+int msu_mlp_s1_width(int C);
 int msu_mlp_s1_launch(int dtype, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
-                      void* y, void* h, long M, void* stream);
+                      void* y, void* h, long M, int C, void* stream);
 
 extern "C" {
 
-// Whether msu_mlp_fused_fwd covers a (channels, hidden) shape: the stage-0 MLP, 96 -> 384 -> 96,
-// and the stage-1 MLP, 192 -> 768 -> 192 (msu_add_ln_mlp_fwd: stage 0 only).
-int msu_mlp_fused_supported(int C, int Hd) { return (C == MC && Hd == MH) || (C == 192 && Hd == 768) ? 1 : 0; }
+// Whether msu_mlp_fused_fwd covers a (channels, hidden) shape: the Swin-T/S stage-0 MLP,
+// 96 -> 384 -> 96, its stage-1 MLP, 192 -> 768 -> 192, and the Swin-B stage-0 MLP,
+// 128 -> 512 -> 128 (msu_add_ln_mlp_fwd: 96 -> 384 only).
+int msu_mlp_fused_supported(int C, int Hd) {
+  return (C == MC && Hd == MH) || (msu_mlp_s1_width(C) && Hd == 4 * C) ? 1 : 0;
+}
 
 // y = fc2(GELU(fc1(x))) with the hidden activation kept on chip; h (nullable) receives the
 // 16-bit pre-activation fc1(x) [M][Hd] for the backward.  dtype bf16 / f16; x, y [M][C] (16-B
-// aligned rows), w1 [Hd][C], w2 [C][Hd] in x's format, b1 [Hd] / b2 [C] f32; (C, Hd) = (96, 384)
-// or (192, 768).
+// aligned rows), w1 [Hd][C], w2 [C][Hd] in x's format, b1 [Hd] / b2 [C] f32; (C, Hd) = (96, 384),
+// (192, 768) or (128, 512).
 int msu_mlp_fused_fwd(int dtype, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                       void* y, void* h, long M, int C, int Hd, void* stream) {
   if (!msu_is16(dtype) || !msu_mlp_fused_supported(C, Hd) || M < 0) return -2;
@@ -323,7 +328,7 @@ int msu_mlp_fused_fwd(int dtype, const void* x, const void* w1, const float* b1,
        15) != 0)
     return -2;
   if (M == 0) return 0;
-  if (C != MC) return msu_mlp_s1_launch(dtype, x, w1, b1, w2, b2, y, h, M, stream);
+  if (C != MC) return msu_mlp_s1_launch(dtype, x, w1, b1, w2, b2, y, h, M, C, stream);
   hipStream_t st = (hipStream_t)stream;
   MlpArgs a{};
   a.x = (const bf16_t*)x;

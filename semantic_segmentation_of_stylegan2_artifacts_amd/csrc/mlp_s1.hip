@@ -1,30 +1,38 @@
-// Stage-1 Swin MLP forward in ONE kernel (torchvision MLP, model_parts.py:538, via the stage-1
-// BasicLayer / BasicLayer_up blocks at dim 192):
+// Swin MLP forward in ONE kernel with the weights streamed through LDS (torchvision MLP,
+// model_parts.py:538), a template over the width C (S1W<C> below):
 //
-//   y = mlp.3(GELU(mlp.0(x)))      x, y: [M][192], hidden 768
+//   y = mlp.3(GELU(mlp.0(x)))      x, y: [M][C], hidden 4 C
 //
-// The GEMM pair this replaces wrote H and GELU(H) (2 x 201 MB at 8 x 128^2 tokens) and read
-// GELU(H) back; here the training form writes H only (the backward's GELU' operand) and GELU(H)
-// never leaves the chip.  Unlike the stage-0 kernel (mlp_fused.hip) the weights (2 x 295 KB) do
-// not fit one CU's LDS, so they are STREAMED: the hidden dimension is cut into 24 chunks of 32
-// units, each chunk's W1 rows [32][192] and W2 columns [192][32] (24 KB) go global -> LDS by
-// LDS-DMA into a ring of NS slots, and the workgroup's waves walk the chunks in step with one
-// barrier per chunk (the slot of chunk j - 1 is refilled with chunk j + NS - 1 as chunk j starts).
-// The ring runs across the workgroup's token tiles as one flat chunk sequence.
+// built for C = 192 (Swin-T/S stage 1, hidden 768) and C = 128 (Swin-B stage 0, hidden 512).
+// The GEMM pair this replaces wrote H and GELU(H) (2 x 201 MB at C = 192, 8 x 128^2 tokens;
+// 2 x 537 MB at C = 128, 8 x 256^2) and read GELU(H) back; here the training form writes H only
+// (the backward's GELU' operand) and GELU(H) never leaves the chip.  Unlike the 96 -> 384 kernel
+// (mlp_fused.hip) the weights (2 x 8 C^2 bytes: 295 KB / 131 KB each) do not fit one CU's LDS
+// beside a ring, so they are STREAMED: the hidden dimension is cut into NU = 4 C / 32 chunks of
+// 32 units, each chunk's W1 rows [32][C] and W2 columns [C][32] (128 C bytes: 24 KB / 16 KB) go
+// global -> LDS by LDS-DMA into a ring of NS slots (6 / 8), and the workgroup's waves walk the
+// chunks in step with one barrier per chunk (interval j refills chunk j - 2's slot with chunk
+// j + NS - 2).  The ring runs across the workgroup's token tiles as one flat chunk sequence.
 //
 // Per wave: a 32-token tile (workgroup: 8 waves, 256 tokens).  The tile's x rows stay in registers
-// as fc1's B operand (12 k steps); per chunk
-//   * fc1 on MFMA (W1 rows as A, tokens on the accumulator columns), + b1, rounded to 16 bits
-//     (stored as H), GELU, rounded again: the unfused epilogues' arithmetic;
+// as fc1's B operand (K1 = C / 16 k steps, C / 4 registers); per chunk
+//   * fc1 on MFMA (K1 MFMAs; W1 rows as A, tokens on the accumulator columns), + b1, rounded to
+//     16 bits (stored as H), GELU, rounded again: the unfused epilogues' arithmetic;
 //   * the packed GELU(H) registers are directly fc2's B operand: the chunk's W1 rows sit in the
 //     slot PERMUTED (slot row rho holds hidden unit pi(rho), pi swapping bits 2 and 3), so that
 //     accumulator registers 8s .. 8s + 7 of lane half hh hold hidden units 16s + 8hh .. + 7 --
 //     consecutive, i.e. ONE 16-B W2 fragment read per fc2 MFMA and one 16-B H store per 8 units;
-//   * fc2 accumulates y^T (six 32-channel tiles, 96 registers) over the 24 chunks.
-// Slot images: W1 rows 384 B with 16-B chunk c at c ^ ((rho >> 1) & 7), W2 rows 64 B with chunk c at
-// c ^ ((row >> 2) & 3): the 16-lane groups of the ds_read_b128 fragment reads cover the 64 banks
-// once.  LDS reads of the ring are untracked inline asm (a compiler-visible ds_read behind a
-// pending LDS-DMA gets a vmcnt(0) that drains the ring); the DMA waits are counted per wave.
+//   * fc2 (2 NCT MFMAs) accumulates y^T (NCT = C / 32 32-channel tiles, C / 2 registers: 96 / 64)
+//     over the NU chunks.
+// Slot images: W1 rows 2 C bytes with 16-B column c at c ^ w1_swz(rho) (C = 192: (rho >> 1) & 7;
+// C = 128: rho & 15), W2 rows 64 B with column c at c ^ ((row >> 2) & 3): the 16-lane groups of
+// the ds_read_b128 fragment reads cover the 64 banks once (asserted below per width).  LDS reads
+// of the ring are untracked inline asm (a compiler-visible ds_read behind a pending LDS-DMA gets
+// a vmcnt(0) that drains the ring); the DMA waits are counted per wave.
+//
+// C = 256 (Swin-B stage 1, hidden 1024) is not built.  This register plan does not fit there (x
+// 64 registers, y^T 128: the instantiation spills 32-48 VGPRs), and no other plan has been tried
+// yet (has the figures and what the measured widths suggest).
 #include "common.h"
 #include "mfma_frag.h"
 
@@ -38,41 +46,129 @@ namespace {
 #define MSU_EXP 0
 #endif
 
-constexpr int SC = 192, SH = 768, SW = 8, STT = 32 * SW;
+constexpr int SW = 8, STT = 32 * SW;
 constexpr int UH = 32;                      // hidden units per chunk (one barrier per chunk)
-constexpr int NU = SH / UH;                 // chunks per token tile (24)
-constexpr int SNS = 6;                      // ring slots (147 KB)
 constexpr int FD = (MSU_EXP & 2) ? 1 : 3;   // fragment reads in flight ahead of the MFMA using one
 constexpr bool STAG = (MSU_EXP & 4) != 0;   // waves 4-7 run half a chunk behind waves 0-3
-constexpr int W1S = UH * SC;                // elements of a slot's W1 image [32][192]
-constexpr int W2S = SC * UH;                // elements of a slot's W2 image [192][32]
-constexpr int SLOT = W1S + W2S;
-constexpr int DMA_PER_UNIT = SLOT * 2 / 1024;  // 1-KB DMA instructions per chunk (24)
-constexpr int DMA_PER_WAVE = DMA_PER_UNIT / SW;
-static_assert(DMA_PER_WAVE * SW == DMA_PER_UNIT, "whole DMA instructions per wave");
 
-struct S1Lds {
-  bf16_t ring[SNS * SLOT];
-  float b1[SH];
-  float b2[SC];
+// The widths the kernel is built for: x, y [M][C], hidden 4 C.  Everything that depends on the
+// width is derived here: a slot holds the chunk's W1 rows [32][C] and W2 columns [C][32]
+// (128 C bytes: 16 KB at C = 128, 24 KB at 192), both halves C / 16 1-KB DMA instructions.
+template <int C>
+struct S1W {
+  static_assert(C == 128 || C == 192, "widths with a register plan and a conflict-free slot image");
+  static constexpr int SC = C, SH = 4 * C;
+  static constexpr int NU = SH / UH;          // chunks per token tile (16 / 24)
+  static constexpr int K1 = C / 16;           // fc1 k steps: a lane's 16-B x loads and y stores per tile
+  static constexpr int NCT = C / 32;          // 32-channel output tiles of fc2
+  static constexpr int CPR = C / 8;           // 16-B columns of a W1 slot row
+  // ring slots (147 KB / 128 KB).  C = 128: 6 / 7 / 8 / 9 slots measured 356 / 352-356 / 349-352 /
+  // 356-359 us with H stored and 282-286 us without for all four (r07a, run-to-run spread ~3 us);
+  // 8 keeps the same 96 KB in flight as the C = 192 ring
+  static constexpr int NS = C == 192 ? 6 : 8;
+  static constexpr int W1S = UH * C;          // elements of a slot's W1 image [32][C]
+  static constexpr int W2S = C * UH;          // elements of a slot's W2 image [C][32]
+  static constexpr int SLOT = W1S + W2S;
+  static constexpr int DMA_W1 = W1S * 2 / 1024;         // 1-KB DMA instructions of the W1 image
+  static constexpr int DMA_PER_UNIT = SLOT * 2 / 1024;  // ... of a chunk (16 / 24)
+  static constexpr int DMA_PER_WAVE = DMA_PER_UNIT / SW;
+  static_assert(DMA_PER_WAVE * SW == DMA_PER_UNIT, "whole DMA instructions per wave");
+  static_assert(NS >= 4 && (NS - 3) * DMA_PER_WAVE + 2 * (NS - 2) <= 63, "steady-state vmcnt fits the counter");
 };
-static_assert(sizeof(S1Lds) <= 160 * 1024, "LDS");
+
+template <int C>
+struct S1Lds {
+  bf16_t ring[S1W<C>::NS * S1W<C>::SLOT];
+  float b1[S1W<C>::SH];
+  float b2[C];
+};
+static_assert(sizeof(S1Lds<128>) <= 160 * 1024 && sizeof(S1Lds<192>) <= 160 * 1024, "LDS");
 
 struct S1Args {
   const bf16_t* x;
-  const bf16_t* w1;  // [768][192]
+  const bf16_t* w1;  // [4 C][C]
   const float* b1;
-  const bf16_t* w2;  // [192][768]
+  const bf16_t* w2;  // [C][4 C]
   const float* b2;
   bf16_t* y;
-  bf16_t* hout;      // H_OUT: [M][768]
+  bf16_t* hout;      // H_OUT: [M][4 C]
   long M;
 };
 
+// index maps: used by the kernel and by the compile-time checks of the slot image
+#define S1_MAP __host__ __device__ __forceinline__ constexpr
 // hidden unit (within a chunk) held by slot row rho: bits 2 and 3 swapped
-MSU_DEV constexpr int s1_pi(int rho) { return (rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1); }
+S1_MAP int s1_pi(int rho) { return (rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1); }
 // 16-B chunk swizzle of a W2 slot row (4 chunks per row)
-MSU_DEV constexpr int w2_swz(int row) { return (row >> 2) & 3; }
+S1_MAP int w2_swz(int row) { return (row >> 2) & 3; }
+// 16-B column swizzle of W1 slot row rho.  C = 192: 384-B rows start on alternating halves of
+// the 256-B bank span, so two rows share a value.  C = 128: rows are one whole bank span, every
+// row starts on bank 0, and 16 rows need 16 different values.
+template <int C>
+S1_MAP int w1_swz(int rho) { return C == 192 ? (rho >> 1) & 7 : rho & 15; }
+
+// ---- the slot image (byte offsets from the slot's start, a multiple of 256 B).  The fragment
+// reads and the DMA below are written with these, and the asserts after them check both.
+// 16-B column c of W1 slot row rho = w1_row_off(rho) + w1_col_off(c, w1_swz(rho))
+template <int C>
+S1_MAP uint32_t w1_row_off(int rho) { return (uint32_t)(rho * C * 2); }
+S1_MAP uint32_t w1_col_off(int c, int sw) { return 16u * (uint32_t)(c ^ sw); }
+// 16-B column c (0 .. 3) of W2 slot row `row` (0 .. C - 1) = w2_row_off(row) + w2_col_off(c, w2_swz(row))
+template <int C>
+S1_MAP uint32_t w2_row_off(int row) { return (uint32_t)(S1W<C>::W1S * 2 + row * UH * 2); }
+S1_MAP uint32_t w2_col_off(int c, int sw) { return 16u * (uint32_t)(c ^ sw); }
+// DMA: the W1 image's 16-B piece p (slot row p / CPR) takes this column of its weight row ...
+template <int C>
+S1_MAP int w1_dma_col(int p) { return (p % S1W<C>::CPR) ^ w1_swz<C>(p / S1W<C>::CPR); }
+// ... and the W2 image's piece p (slot row p / 4) this 16-B column of the chunk's 32 hidden units
+S1_MAP int w2_dma_col(int p) { return (p & 3) ^ w2_swz(p >> 2); }
+
+// ds_read_b128 resolves bank conflicts within four groups of 16 lanes: lanes {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31} and the same plus 32.  Lane i (0 .. 15) of group g (0 .. 3):
+constexpr int b128_group_lane(int g, int i) {
+  const int l = (g & 1) == 0 ? (i < 4 ? i : i < 8 ? i + 8 : i + 12) : (i < 8 ? i + 4 : i < 12 ? i + 8 : i + 16);
+  return l + 32 * (g >> 1);
+}
+// every fc1 / fc2 fragment read puts each group's 16 lanes on 16 distinct 16-B bank columns
+template <int C>
+constexpr bool s1_reads_conflict_free() {
+  for (int g = 0; g < 4; ++g) {
+    for (int ks = 0; ks < S1W<C>::K1; ++ks) {
+      unsigned cols = 0;
+      for (int i = 0; i < 16; ++i) {
+        const int lane = b128_group_lane(g, i), tl = lane & 31, hh = lane >> 5;
+        cols |= 1u << (((w1_row_off<C>(tl) + w1_col_off(2 * ks + hh, w1_swz<C>(tl))) >> 4) & 15);
+      }
+      if (cols != 0xffffu) return false;
+    }
+    for (int ct = 0; ct < S1W<C>::NCT; ++ct)
+      for (int s = 0; s < 2; ++s) {
+        unsigned cols = 0;
+        for (int i = 0; i < 16; ++i) {
+          const int lane = b128_group_lane(g, i), tl = lane & 31, hh = lane >> 5;
+          cols |= 1u << (((w2_row_off<C>(32 * ct + tl) + w2_col_off(2 * s + hh, w2_swz(32 * ct + tl))) >> 4) & 15);
+        }
+        if (cols != 0xffffu) return false;
+      }
+  }
+  return true;
+}
+// the DMA writes the image the reads expect: piece p lands at byte 16 p of its half of the slot
+template <int C>
+constexpr bool s1_dma_writes_image() {
+  for (int p = 0; p < UH * S1W<C>::CPR; ++p) {
+    const int rho = p / S1W<C>::CPR;
+    if (w1_row_off<C>(rho) + w1_col_off(w1_dma_col<C>(p), w1_swz<C>(rho)) != 16u * (uint32_t)p) return false;
+  }
+  for (int p = 0; p < C * 4; ++p) {
+    const int row = p >> 2;
+    if (w2_row_off<C>(row) + w2_col_off(w2_dma_col(p), w2_swz(row)) != (uint32_t)(S1W<C>::W1S * 2) + 16u * (uint32_t)p)
+      return false;
+  }
+  return true;
+}
+static_assert(s1_reads_conflict_free<128>() && s1_reads_conflict_free<192>(), "slot image: bank conflicts");
+static_assert(s1_dma_writes_image<128>() && s1_dma_writes_image<192>(), "slot image: DMA and reads disagree");
 
 // s_waitcnt vmcnt(n) for a wave-uniform runtime n (capped: waiting for more is always safe)
 MSU_DEV void wait_vmcnt_le(int n) {
@@ -95,18 +191,23 @@ MSU_DEV bf16x8 ds_b128_untracked(uint32_t addr) {
   return v;
 }
 
-// Per chunk a wave runs three phases: fc1 (12 MFMAs), the epilogue (b1, H, GELU: VALU), fc2 (12
-// MFMAs).  With one barrier per chunk the two waves of a SIMD (w, w + 4) would run them in phase --
-// both on MFMAs, then both on VALU.  So waves 4-7 are STAGGERED: in the interval after chunk j's
-// barrier waves 0-3 run fc1(j), epi(j), fc2(j) while waves 4-7 run epi(j - 1), fc2(j - 1), fc1(j)
-// (their fc1 accumulator crosses the barrier): each SIMD pairs one wave's MFMAs with the other's
-// VALU.  Chunk j - 1's slot is then read up to the end of interval j, so the ring prefetches
-// SNS - 2 chunks ahead and interval j refills chunk j - 2's slot; one extra interval at the end
-// lets waves 4-7 finish the last chunk.
-template <typename T, bool H_OUT>
+// Per chunk a wave runs three phases: fc1 (K1 = C / 16 MFMAs), the epilogue (b1, H, GELU: VALU),
+// fc2 (2 NCT = C / 16 MFMAs).  In every real build (MSU_EXP = 0) all eight waves run fc1(j),
+// epi(j), fc2(j) in the interval after chunk j's barrier.
+// The MSU_EXP & 4 variant (STAG; measured slower, r06h) STAGGERS waves 4-7: with one barrier per
+// chunk the two waves of a SIMD (w, w + 4) run the phases in phase -- both on MFMAs, then both on
+// VALU -- so there waves 4-7 run epi(j - 1), fc2(j - 1), fc1(j) in interval j (their fc1
+// accumulator crosses the barrier) and each SIMD pairs one wave's MFMAs with the other's VALU.
+// The ring is laid out for that variant too: chunk j - 1's slot may be read up to the end of
+// interval j, so the ring prefetches SNS - 2 chunks ahead and interval j refills chunk j - 2's
+// slot; one extra interval at the end lets staggered waves finish the last chunk.
+template <typename T, bool H_OUT, int C>
 __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
+  using W = S1W<C>;
+  constexpr int SC = W::SC, SH = W::SH, NU = W::NU, SNS = W::NS, K1 = W::K1, NCT = W::NCT;
+  constexpr int W1S = W::W1S, SLOT = W::SLOT, DMA_W1 = W::DMA_W1, DMA_PER_WAVE = W::DMA_PER_WAVE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  S1Lds& L = *reinterpret_cast<S1Lds*>(smem_raw);
+  S1Lds<C>& L = *reinterpret_cast<S1Lds<C>*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, tl = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool late = STAG && wave >= 4;  // wave-uniform
@@ -122,34 +223,33 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
   for (int s = tid; s < SC; s += 64 * SW) L.b2[s] = A.b2[s];
   __syncthreads();  // before any LDS-DMA is in flight (this barrier drains nothing)
 
-  // chunk q (0 .. 23) of the weights into ring slot `slot`: this wave's 3 of the chunk's 24 1-KB
-  // DMA instructions (W1 rows permuted by pi and chunk-swizzled; W2 columns chunk-swizzled)
+  // chunk q (0 .. NU - 1) of the weights into ring slot `slot`: this wave's share (C / 64) of the
+  // chunk's C / 8 1-KB DMA instructions (W1 rows permuted by pi and chunk-swizzled; W2 columns
+  // chunk-swizzled)
   auto dma_unit = [&](int q, int slot) __attribute__((always_inline)) {
     bf16_t* base = L.ring + slot * SLOT;
     const int ln = opaque(lane);
 #pragma unroll
     for (int r = 0; r < DMA_PER_WAVE; ++r) {
       const int i = wave + SW * r;  // instruction (wave-uniform)
-      if (i < 12) {
-        const int p = 64 * i + ln, rho = p / 24, pos = p - (p / 24) * 24;
-        const int gc = pos ^ ((rho >> 1) & 7);
-        glds16(A.w1 + (long)(UH * q + s1_pi(rho)) * SC + 8 * gc, base + 512 * i);
+      if (i < DMA_W1) {
+        const int p = 64 * i + ln, rho = p / W::CPR;
+        glds16(A.w1 + (long)(UH * q + s1_pi(rho)) * SC + 8 * w1_dma_col<C>(p), base + 512 * i);
       } else {
-        const int i2 = i - 12;
-        const int p = 64 * i2 + ln, row = p >> 2, pos = p & 3;
-        const int gc = pos ^ w2_swz(row);
-        glds16(A.w2 + (long)row * SH + UH * q + 8 * gc, base + W1S + 512 * i2);
+        const int i2 = i - DMA_W1;
+        const int p = 64 * i2 + ln, row = p >> 2;
+        glds16(A.w2 + (long)row * SH + UH * q + 8 * w2_dma_col(p), base + W1S + 512 * i2);
       }
     }
   };
   // the tile's token rows as fc1's B operand: lane (token tl, half hh) holds k = 16 ks + 8 hh .. + 7
-  u32x4 xc[12];
+  u32x4 xc[K1];
   auto load_x = [&](long t) __attribute__((always_inline)) {
     const long row = t * STT + 32 * wave + tl;
     const bool ok = row < M;
     const bf16_t* p = A.x + (ok ? row : 0) * SC + 8 * hh;
 #pragma unroll
-    for (int ks = 0; ks < 12; ++ks) {
+    for (int ks = 0; ks < K1; ++ks) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(p + 16 * ks);
       xc[ks] = ok ? v : u32x4{0u, 0u, 0u, 0u};
     }
@@ -162,7 +262,7 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
   int issued = 0;
   int mark[SNS - 2];
   load_x(first);
-  issued += 12;
+  issued += K1;
   int mark_x = issued;
 #pragma unroll
   for (int s = 0; s < SNS - 2; ++s) {
@@ -173,15 +273,15 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
     mark[s] = issued;
   }
 
-  f32x16 yacc[6];
+  f32x16 yacc[NCT];
 #pragma unroll
-  for (int ct = 0; ct < 6; ++ct) yacc[ct] = f32x16{0};
+  for (int ct = 0; ct < NCT; ++ct) yacc[ct] = f32x16{0};
   f32x16 h = f32x16{0};  // fc1 accumulator (waves 4-7: carried to the next interval)
   // untracked-read lane addresses (bytes)
   const uint32_t ring0 = lds_u32(L.ring);
-  const uint32_t a1_lane = (uint32_t)(tl * SC * 2);              // + slot, + 16 * pos(ks)
-  const int w1sw = (tl >> 1) & 7;
-  const uint32_t a2_lane = (uint32_t)(W1S * 2 + tl * UH * 2);    // + slot, + 2048 ct, + 16 * pos
+  const uint32_t a1_lane = w1_row_off<C>(tl);                    // + slot, + 16 * pos(ks)
+  const int w1sw = w1_swz<C>(tl);
+  const uint32_t a2_lane = w2_row_off<C>(tl);                    // + slot, + 2048 ct, + 16 * pos
   const int w2sw = w2_swz(tl);                                   // (32 ct + tl: same swizzle)
   const uint32_t b1_lane = lds_u32(L.b1) + 4u * (uint32_t)(8 * hh);
   const uint32_t b2_lane = lds_u32(L.b2) + 4u * (uint32_t)(4 * hh);
@@ -191,12 +291,12 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
     const uint32_t a1 = ring0 + (uint32_t)(slot * SLOT * 2) + a1_lane;
     h = f32x16{0};
     bf16x8 wf[FD + 1];
-    auto addr1 = [&](int ks) { return a1 + 16u * (uint32_t)((2 * ks + hh) ^ w1sw); };
+    auto addr1 = [&](int ks) { return a1 + w1_col_off(2 * ks + hh, w1sw); };
     unroll_for<FD>([&](auto KS) { wf[decltype(KS)::value] = ds_b128_untracked<0>(addr1(decltype(KS)::value)); });
-    unroll_for<12>([&](auto KS) {
+    unroll_for<K1>([&](auto KS) {
       constexpr int ks = decltype(KS)::value;
-      if constexpr (ks + FD < 12) wf[(ks + FD) % (FD + 1)] = ds_b128_untracked<0>(addr1(ks + FD));
-      lds_wait_tie<(ks + FD < 12 ? FD : 11 - ks)>(wf[ks % (FD + 1)]);
+      if constexpr (ks + FD < K1) wf[(ks + FD) % (FD + 1)] = ds_b128_untracked<0>(addr1(ks + FD));
+      lds_wait_tie<(ks + FD < K1 ? FD : K1 - 1 - ks)>(wf[ks % (FD + 1)]);
       if constexpr (MSU_EXP & 64) {
         const bf16x8 wv = wf[ks % (FD + 1)];
         const u32x4 xv = xc[ks];
@@ -243,19 +343,19 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
     }
     if (H_OUT && !(MSU_EXP & 16) && t * STT + 32 * wave + 32 <= M) issued += 2;
   };
-  // y^T[c][t] += W2[c][chunk] . GELU(H)^T: six 32-channel tiles, two 16-deep k steps
+  // y^T[c][t] += W2[c][chunk] . GELU(H)^T: C / 32 32-channel tiles, two 16-deep k steps
   auto fc2 = [&](int slot, const u32x4 (&g)[2]) __attribute__((always_inline)) {
     const uint32_t a2 = ring0 + (uint32_t)(slot * SLOT * 2) + a2_lane;
-    auto addr2 = [&](int ct, int s) { return a2 + (uint32_t)(ct * 32 * UH * 2) + 16u * (uint32_t)((2 * s + hh) ^ w2sw); };
+    auto addr2 = [&](int ct, int s) { return a2 + (uint32_t)(ct * 32 * UH * 2) + w2_col_off(2 * s + hh, w2sw); };
     bf16x8 af[FD + 1];
     unroll_for<FD>([&](auto I) {
       constexpr int i = decltype(I)::value;
-      af[i] = ds_b128_untracked<0>(addr2(i % 6, i / 6));
+      af[i] = ds_b128_untracked<0>(addr2(i % NCT, i / NCT));
     });
-    unroll_for<12>([&](auto I) {
-      constexpr int i = decltype(I)::value, s = i / 6, ct = i % 6;
-      if constexpr (i + FD < 12) af[(i + FD) % (FD + 1)] = ds_b128_untracked<0>(addr2((i + FD) % 6, (i + FD) / 6));
-      lds_wait_tie<(i + FD < 12 ? FD : 11 - i)>(af[i % (FD + 1)]);
+    unroll_for<2 * NCT>([&](auto I) {
+      constexpr int i = decltype(I)::value, s = i / NCT, ct = i % NCT;
+      if constexpr (i + FD < 2 * NCT) af[(i + FD) % (FD + 1)] = ds_b128_untracked<0>(addr2((i + FD) % NCT, (i + FD) / NCT));
+      lds_wait_tie<(i + FD < 2 * NCT ? FD : 2 * NCT - 1 - i)>(af[i % (FD + 1)]);
       if constexpr (MSU_EXP & 32) {
         const bf16x8 av = af[i % (FD + 1)];
         const u32x4 gv = g[s];
@@ -270,7 +370,7 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
     const bool ok = row < M;
     bf16_t* yr = A.y + (ok ? row : 0) * SC;
 #pragma unroll
-    for (int ct = 0; ct < 6; ++ct) {
+    for (int ct = 0; ct < NCT; ++ct) {
       uint32_t w[8];
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
@@ -290,7 +390,7 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
       }
       yacc[ct] = f32x16{0};
     }
-    if (t * STT + 32 * wave + 32 <= M) issued += 12;
+    if (t * STT + 32 * wave + 32 <= M) issued += 2 * NCT;
   };
   // fc1 of chunk (q, slot) of tile t, after which the last chunk of a tile loads the next tile's x
   auto fc1_step = [&](int q, int slot, long t) __attribute__((always_inline)) {
@@ -298,7 +398,7 @@ __global__ void __launch_bounds__(64 * SW) mlp_s1_kernel(S1Args A) {
     fc1(slot);
     if (q == NU - 1 && t + G < ntiles) {  // xc is free once the tile's last fc1 has issued
       load_x(t + G);
-      issued += 12;
+      issued += K1;
       mark_x = issued;
     }
   };
@@ -366,12 +466,12 @@ int num_cus_s1() {
   return cus;
 }
 
-template <typename T, bool H_OUT>
+template <typename T, bool H_OUT, int C>
 int launch_s1(const S1Args& a, hipStream_t st) {
-  auto kern = mlp_s1_kernel<T, H_OUT>;
-  static bool attr_set = false;
+  auto kern = mlp_s1_kernel<T, H_OUT, C>;
+  static bool attr_set = false;  // one per instantiation: each kernel needs its own attribute
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(S1Lds)) !=
+    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(S1Lds<C>)) !=
         hipSuccess)
       return -4;
     attr_set = true;
@@ -379,15 +479,19 @@ int launch_s1(const S1Args& a, hipStream_t st) {
   const long ntiles = (a.M + STT - 1) / STT;
   long grid = num_cus_s1();
   if (grid > ntiles) grid = ntiles;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * SW), sizeof(S1Lds), st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * SW), sizeof(S1Lds<C>), st, a);
   return MSU_CHECK_LAUNCH();
 }
 
 }  // namespace
 
-// the stage-1 form of msu_mlp_fused_fwd (mlp_fused.hip dispatches here for C = 192, Hd = 768)
+// whether the streamed-weight kernel is built for x, y [M][C] (hidden 4 C)
+int msu_mlp_s1_width(int C) { return C == 128 || C == 192; }
+
+// the streamed-weight form of msu_mlp_fused_fwd (mlp_fused.hip dispatches here for the widths of
+// msu_mlp_s1_width: Swin-B stage 0, C = 128, and Swin-T/S stage 1, C = 192)
 int msu_mlp_s1_launch(int dtype, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
-                      void* y, void* h, long M, void* stream) {
+                      void* y, void* h, long M, int C, void* stream) {
   S1Args a{};
   a.x = (const bf16_t*)x;
   a.w1 = (const bf16_t*)w1;
@@ -398,10 +502,17 @@ int msu_mlp_s1_launch(int dtype, const void* x, const void* w1, const float* b1,
   a.hout = (bf16_t*)h;
   a.M = M;
   hipStream_t st = (hipStream_t)stream;
-  if (h != nullptr) {
-    MSU_DISPATCH16(dtype, T, return (launch_s1<T, true>(a, st)));
-  } else {
-    MSU_DISPATCH16(dtype, T, return (launch_s1<T, false>(a, st)));
+#define MSU_S1_WIDTH(CC)                                                \
+  if (C == CC) {                                                        \
+    if (h != nullptr) {                                                 \
+      MSU_DISPATCH16(dtype, T, return (launch_s1<T, true, CC>(a, st))); \
+    } else {                                                            \
+      MSU_DISPATCH16(dtype, T, return (launch_s1<T, false, CC>(a, st)));\
+    }                                                                   \
+    return -3;                                                          \
   }
-  return -3;
+  MSU_S1_WIDTH(128)
+  MSU_S1_WIDTH(192)
+#undef MSU_S1_WIDTH
+  return -2;
 }

@@ -107,12 +107,15 @@ for s in "$@"; do
       cat $O/${TAG}_kern.log ;;
     gelu_tests) step gelu_tests 900 $PYT -m gpu $R/tests/test_gpu_tok_gemm.py $R/tests/test_gpu_nt_gemm.py \
                   $R/tests/test_gpu_linbwd.py $R/tests/test_gpu_ln_side.py $R/tests/test_gpu_ops.py ;;
-    mlp_s1) step mlp_s1 200 python -u $R/tools/mlp_s1_one.py 20 ;;
+    mlp_s1) step mlp_s1 200 python -u $R/tools/mlp_s1_one.py ${S1_C:-192} ${S1_M:-131072} 20 ;;
     mlp_s1_ab)
-      # stage-1 fused MLP: this build vs AB_LIB (kernel times twice each, then AB_LIB's MLP tests)
+      # streamed-weight fused MLP: this build vs AB_LIB (kernel times twice each, then AB_LIB's MLP
+      # tests).  Width / tokens from S1_C / S1_M (default 192 / 131072); AB_LIB must have a fused
+      # kernel for S1_C (a library from before the C = 128 instantiation has 192 only), else the
+      # tool says so and times the pair in both arms of that library
       for L in "" "$AB_LIB" "" "$AB_LIB"; do
         echo "== ${L:-cur}" >> $O/${TAG}_mlp_s1_ab.log
-        MSU_LIB_OVERRIDE=$L timeout -k 10 200 python -u $R/tools/mlp_s1_one.py 20 >> $O/${TAG}_mlp_s1_ab.log 2>&1 || exit 3
+        MSU_LIB_OVERRIDE=$L timeout -k 10 200 python -u $R/tools/mlp_s1_one.py ${S1_C:-192} ${S1_M:-131072} 20 >> $O/${TAG}_mlp_s1_ab.log 2>&1 || exit 3
       done
       cat $O/${TAG}_mlp_s1_ab.log
       MSU_LIB_OVERRIDE=$AB_LIB step mlp_tests_B 600 $PYT -m gpu $R/tests/test_gpu_mlp_infer.py ;;
@@ -174,7 +177,7 @@ for s in "$@"; do
       # stage-1 fused MLP variants (tools/build_exp.sh mlp_s1 1 2): kernel times, twice each
       for r in 1 2; do for L in "" $R/tools/exp/libmsunet_mlp_s1_1.so $R/tools/exp/libmsunet_mlp_s1_2.so; do
         echo "== ${L:-cur}" >> $O/${TAG}_mlp_s1_var.log
-        MSU_LIB_OVERRIDE=$L timeout -k 10 200 python -u $R/tools/mlp_s1_one.py 20 2>&1 | grep fused >> $O/${TAG}_mlp_s1_var.log || exit 3
+        MSU_LIB_OVERRIDE=$L timeout -k 10 200 python -u $R/tools/mlp_s1_one.py ${S1_C:-192} ${S1_M:-131072} 20 2>&1 | grep fused >> $O/${TAG}_mlp_s1_var.log || exit 3
       done; done
       cat $O/${TAG}_mlp_s1_var.log ;;
     ln_exp)
