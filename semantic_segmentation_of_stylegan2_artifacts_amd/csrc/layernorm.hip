@@ -538,9 +538,6 @@ int launch_fwd(const LnArgs& a, hipStream_t st, int max_blocks) {
   }
   if (nchunk <= 32) return go(ln_fwd_kernel<T, MODE, 32, 1>, 32);
   if (nchunk <= 64) return go(ln_fwd_kernel<T, MODE, 64, 1>, 64);
-  if (nchunk <= 4 * 4) return go(ln_fwd_kernel<T, MODE, 4, 4>, 4);
-  if (nchunk <= 8 * 4) return go(ln_fwd_kernel<T, MODE, 8, 4>, 8);
-  if (nchunk <= 16 * 4) return go(ln_fwd_kernel<T, MODE, 16, 4>, 16);
   if (nchunk <= 32 * 4) return go(ln_fwd_kernel<T, MODE, 32, 4>, 32);
   if (nchunk <= 64 * 4) return go(ln_fwd_kernel<T, MODE, 64, 4>, 64);
   if (nchunk <= 64 * 8) return go(ln_fwd_kernel<T, MODE, 64, 8>, 64);
@@ -558,19 +555,30 @@ int launch_bwd(const LnBwdArgs& a, hipStream_t st, int nblocks) {
   if (nchunk <= 16) return go(ln_bwd_kernel<T, MODE, 16, 1>);
   if (nchunk <= 32) return go(ln_bwd_kernel<T, MODE, 32, 1>);
   if (nchunk <= 64) return go(ln_bwd_kernel<T, MODE, 64, 1>);
-  if (nchunk <= 4 * 3) return go(ln_bwd_kernel<T, MODE, 4, 3>);  // C = 96 bf16: no idle slot
-  if (nchunk <= 4 * 4) return go(ln_bwd_kernel<T, MODE, 4, 4>);
-  if (nchunk <= 8 * 4) return go(ln_bwd_kernel<T, MODE, 8, 4>);
-  if (nchunk <= 16 * 4) return go(ln_bwd_kernel<T, MODE, 16, 4>);
   if (nchunk <= 32 * 4) return go(ln_bwd_kernel<T, MODE, 32, 4>);
   if (nchunk <= 64 * 4) return go(ln_bwd_kernel<T, MODE, 64, 4>);
   if (nchunk <= 64 * 8) return go(ln_bwd_kernel<T, MODE, 64, 8>);
   return -2;
 }
 
+// shapes no kernel here can address: rows of whole 16-B chunks, at most 2048 wide; in merge
+// mode a chunk must lie inside one of the four gathered quadrants (Cin a multiple of the chunk
+// too, else src_off reads across two quadrants and past the tensor) and the grid splits into
+// whole 2x2 patches (PatchMerging asserts H, W even).  Checked before any launch or HIP call.
+template <int MODE, typename A>
+bool shape_ok(int dtype, const A& a) {
+  const int vw = msu_is16(dtype) ? 8 : 4;
+  if (a.C <= 0 || a.C % vw != 0 || a.C > 2048) return false;
+  if constexpr (MODE == IN_MERGE) {
+    if (a.Cin <= 0 || a.Cin % vw != 0 || a.C != 4 * a.Cin) return false;
+    if (a.H < 2 || a.W < 2 || (a.H & 1) || (a.W & 1)) return false;
+  }
+  return true;
+}
+
 template <int MODE>
 int fwd_dispatch(int dtype, const LnArgs& a, hipStream_t st) {
-  if (a.C % (msu_is16(dtype) ? 8 : 4) != 0 || a.C > 2048) return -2;
+  if (!shape_ok<MODE>(dtype, a)) return -2;
   if (a.rows == 0) return 0;
   // grid cap 4096 blocks: with the next row prefetched (r04y) a group needs several rows to
   // overlap loads with the normalisation; at 16384 the C >= 192 launches ran one row per group
@@ -584,7 +592,7 @@ int fwd_dispatch(int dtype, const LnArgs& a, hipStream_t st) {
 template <int MODE>
 int bwd_dispatch(int dtype, const LnBwdArgs& a, float* dgamma, float* dbeta, int nparts, int accumulate,
                  hipStream_t st) {
-  if (a.C % (msu_is16(dtype) ? 8 : 4) != 0 || a.C > 2048) return -2;
+  if (!shape_ok<MODE>(dtype, a)) return -2;
   if (a.rows == 0) return 0;
   int rc = -3;
   // the parameter-gradient partials summed by the kernel's last blocks (16-B aligned rows and
@@ -776,7 +784,10 @@ __global__ void __launch_bounds__(256) head_fwd16_kernel(const T* z, const float
       for (int k = 0; k < KC; ++k)
 #pragma unroll
         for (int e = 0; e < 8; ++e) sum += v[h][k][e];
-      const float mu = group_sum<TPR>(sum) * (1.0f / C);
+      // a true division, like every other kernel here: with sum * (1 / C) the 1 / 96 is inexact and
+      // v - mu contracts to fma(-sum, 1 / C, v), so a constant row (sum / C exact, rstd = eps^-1/2)
+      // kept d = -2^-25 |mu| instead of 0 and its logit was off by rstd d sum(gamma w)
+      const float mu = group_sum<TPR>(sum) / C;
       float var = 0.f, dot = 0.f;
 #pragma unroll
       for (int k = 0; k < KC; ++k)

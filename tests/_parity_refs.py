@@ -10,6 +10,9 @@
 * ``conv3x3_ref``: ``conv2d(a, W, b, padding=1)`` on NHWC tensors as nine shifted fp32
   matmuls (autograd gives dA, dW, db), so the 1024^2 references need neither the CPU nor a
   library convolution.
+* ``ln_plain_ref`` / ``ln_add_ref`` / ``ln_merge_ref`` / ``ln_d2s2_ref`` / ``ln_head_ref``: the
+  four input modes of csrc/layernorm.hip and its 1-channel head in float64 (the one exception to
+  "fp32" above: tests/test_gpu_ln_matrix.py judges f32 kernels against them).
 """
 import math
 
@@ -93,3 +96,116 @@ def d2s4(x, C):
     """FinalPatchExpand_X4_V2's rearrange 'b h w (p1 p2 c) -> b (h p1) (w p2) c' (p = 4)."""
     B, h, w, _ = x.shape
     return x.view(B, h, w, 4, 4, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 4 * h, 4 * w, C)
+
+
+# ----------------------------------------------------------------------------- LayerNorm family
+# fp64 references of csrc/layernorm.hip, one per input mode, evaluated on the tensors' device.
+# Each takes what the kernel takes, already rounded to the storage type, and returns a dict of
+# fp64 tensors: y, mean, rstd, the LayerNorm input rows ``xr`` [rows, C] (for the error bounds)
+# and, through autograd, dx (in the source layout), dgamma, dbeta (+ db / s in add mode).
+def _ln64(xr, gamma, beta, eps):
+    mean = xr.mean(-1, keepdim=True)
+    var = ((xr - mean) ** 2).mean(-1, keepdim=True)
+    rstd = (var + eps).rsqrt()
+    return (xr - mean) * rstd * gamma + beta, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+def _ln_mode_ref(build_rows, srcs, gamma, beta, dy, eps, extra=None):
+    """build_rows(*fp64 leaves) -> (LayerNorm input rows [rows, C], dict of extra outputs)."""
+    leaves = [s.detach().double().requires_grad_(True) for s in srcs]
+    g = gamma.detach().double().requires_grad_(True)
+    b = beta.detach().double().requires_grad_(True)
+    xr, out = build_rows(*leaves)
+    y, mean, rstd = _ln64(xr, g, b, eps)
+    out.update(y=y.detach(), mean=mean.detach(), rstd=rstd.detach(), xr=xr.detach())
+    if dy is not None:
+        loss = (y * dy.detach().double().reshape(y.shape)).sum()
+        if extra is not None:
+            loss = loss + extra(xr)
+        grads = torch.autograd.grad(loss, leaves + [g, b])
+        out.update(grads=[t.detach() for t in grads[:-2]], dgamma=grads[-2].detach(), dbeta=grads[-1].detach())
+    return out
+
+
+def ln_plain_ref(x, gamma, beta, dy=None, eps=1e-5, dres=()):
+    """LayerNorm over the last dim; dres: further gradients of x (summed into dx)."""
+    C = x.shape[-1]
+    extra = (lambda xr: sum((xr * r.detach().double().reshape(-1, C)).sum() for r in dres)) if dres else None
+    out = _ln_mode_ref(lambda xs: (xs.reshape(-1, C), {}), [x], gamma, beta, dy, eps, extra)
+    if dy is not None:
+        out["dx"] = out.pop("grads")[0]
+    return out
+
+
+def ln_add_ref(a, b, scale, rows_per_sample, gamma, beta, dy=None, eps=1e-5, dres=(), s=None):
+    """s = a + scale[row // rows_per_sample] * b, y = LN(s).  The kernel rounds s to the storage
+    type and normalises that rounded value: given the kernel's own ``s``, y and the backward are
+    evaluated at it (its gradient still flows to a and b), while ``s`` of the result stays the
+    exact fp64 sum.  b / scale may be None (s = a / scale 1)."""
+    C = a.shape[-1]
+    rows = a.numel() // C
+    sc = None
+    if scale is not None:
+        idx = torch.arange(rows, device=a.device) // rows_per_sample
+        sc = scale.detach().double()[idx].unsqueeze(-1)
+    srcs = [a] if b is None else [a, b]
+
+    def build(a64, b64=None):
+        s64 = a64.reshape(-1, C)
+        if b64 is not None:
+            s64 = s64 + (b64.reshape(-1, C) if sc is None else sc * b64.reshape(-1, C))
+        used = s64 if s is None else s64 + (s.detach().double().reshape(-1, C) - s64).detach()
+        return used, {"s": s64.detach()}
+
+    extra = (lambda xr: sum((xr * r.detach().double().reshape(-1, C)).sum() for r in dres)) if dres else None
+    out = _ln_mode_ref(build, srcs, gamma, beta, dy, eps, extra)
+    out["scale_rows"] = sc
+    if dy is not None:
+        grads = out.pop("grads")
+        out["dx"] = grads[0]
+        out["db"] = grads[1] if b is not None else (grads[0] if sc is None else grads[0].reshape(-1, C) * sc)
+    return out
+
+
+def merge_rows(x):
+    """PatchMerging's gather: [B, H, W, Cin] -> [B * H/2 * W/2, 4 Cin] in x0, x1, x2, x3 order."""
+    B, H, W, Cin = x.shape
+    assert H % 2 == 0 and W % 2 == 0
+    x0, x1, x2, x3 = x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]
+    return torch.cat([x0, x1, x2, x3], -1).reshape(-1, 4 * Cin)
+
+
+def d2s2_rows(x):
+    """PatchExpand's rearrange 'b h w (p1 p2 c) -> b (h p1) (w p2) c' (p = 2) as view / permute:
+    [B, H, W, 4c] -> [B * 2H * 2W, c]."""
+    B, H, W, C4 = x.shape
+    c = C4 // 4
+    return x.reshape(B, H, W, 2, 2, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, c)
+
+
+def ln_merge_ref(x, gamma, beta, dy=None, eps=1e-5):
+    out = _ln_mode_ref(lambda xs: (merge_rows(xs), {}), [x], gamma, beta, dy, eps)
+    if dy is not None:
+        out["dx"] = out.pop("grads")[0]
+    return out
+
+
+def ln_d2s2_ref(x, gamma, beta, dy=None, eps=1e-5):
+    out = _ln_mode_ref(lambda xs: (d2s2_rows(xs), {}), [x], gamma, beta, dy, eps)
+    if dy is not None:
+        out["dx"] = out.pop("grads")[0]
+    return out
+
+
+def ln_head_ref(z, gamma, beta, w, dlogit=None, eps=1e-5):
+    """logit[r] = <LN(z[r]), w> (the 1-channel output head); dz, dgamma, dbeta, dw by autograd."""
+    C = z.shape[-1]
+    z64 = z.detach().double().reshape(-1, C).requires_grad_(True)
+    g, b, w64 = (t.detach().double().reshape(-1).requires_grad_(True) for t in (gamma, beta, w))
+    y, mean, rstd = _ln64(z64, g, b, eps)
+    logit = (y * w64).sum(-1)
+    out = dict(logit=logit.detach(), mean=mean.detach(), rstd=rstd.detach(), xr=z64.detach(), y=y.detach())
+    if dlogit is not None:
+        dz, dg, db, dw = torch.autograd.grad((logit * dlogit.detach().double().reshape(-1)).sum(), (z64, g, b, w64))
+        out.update(dz=dz, dgamma=dg, dbeta=db, dw=dw)
+    return out
