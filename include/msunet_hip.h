@@ -269,8 +269,8 @@ int msu_nt_gemm_kn(int dtype, const void* A, const void* Wk, const float* bias, 
  * layers_cent1[-1] / layers_cent2[-1], model_parts.py:795 / :807, and evaluation).  x, y [M][C],
  * w1 [Hd][C], w2 [C][Hd] in the 16-bit format dtype, b1 / b2 f32, all 16-B aligned.
  * msu_mlp_fused_supported(C, Hd): 1 for (C, Hd) = (96, 384) (Swin-T/S stage 0, weights resident
- * in LDS), (192, 768) (Swin-T/S stage 1) and (128, 512) (Swin-B stage 0; both with the weights
- * streamed through an LDS ring).  Returns 0, -2 (unsupported).
+ * in LDS), (192, 768) (Swin-T/S stage 1), (128, 512) and (256, 1024) (Swin-B stages 0 and 1; all
+ * three with the weights streamed through an LDS ring).  Returns 0, -2 (unsupported).
  * The backward's mlp.3 step at (96, 384) is msu_linear_bwd with X = null and H = h. */
 int msu_mlp_fused_supported(int C, int Hd);
 /* No-grad second half of a stage-0 block: s_out = a + bscale[sample] * br (16-bit; bscale null = 1,

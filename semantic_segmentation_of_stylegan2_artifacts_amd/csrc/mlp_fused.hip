@@ -303,7 +303,7 @@ int launch_mlp(const MlpArgs& a, hipStream_t st) {
 }  // namespace
 
 // mlp_s1.hip: the streamed-weight form (weights through an LDS ring; hidden 4 C) and its widths
-// (C = 192: Swin-T/S stage 1; C = 128: Swin-B stage 0)
+// (C = 192: Swin-T/S stage 1; C = 128 / 256: Swin-B stages 0 / 1)
 int msu_mlp_s1_width(int C);
 int msu_mlp_s1_launch(int dtype, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                       void* y, void* h, long M, int C, void* stream);
@@ -311,8 +311,8 @@ int msu_mlp_s1_launch(int dtype, const void* x, const void* w1, const float* b1,
 extern "C" {
 
 // Whether msu_mlp_fused_fwd covers a (channels, hidden) shape: the Swin-T/S stage-0 MLP,
-// 96 -> 384 -> 96, its stage-1 MLP, 192 -> 768 -> 192, and the Swin-B stage-0 MLP,
-// 128 -> 512 -> 128 (msu_add_ln_mlp_fwd: 96 -> 384 only).
+// 96 -> 384 -> 96, its stage-1 MLP, 192 -> 768 -> 192, and the Swin-B stage-0 and stage-1 MLPs,
+// 128 -> 512 -> 128 and 256 -> 1024 -> 256 (msu_add_ln_mlp_fwd: 96 -> 384 only).
 int msu_mlp_fused_supported(int C, int Hd) {
   return (C == MC && Hd == MH) || (msu_mlp_s1_width(C) && Hd == 4 * C) ? 1 : 0;
 }
@@ -320,7 +320,7 @@ int msu_mlp_fused_supported(int C, int Hd) {
 // y = fc2(GELU(fc1(x))) with the hidden activation kept on chip; h (nullable) receives the
 // 16-bit pre-activation fc1(x) [M][Hd] for the backward.  dtype bf16 / f16; x, y [M][C] (16-B
 // aligned rows), w1 [Hd][C], w2 [C][Hd] in x's format, b1 [Hd] / b2 [C] f32; (C, Hd) = (96, 384),
-// (192, 768) or (128, 512).
+// (192, 768), (128, 512) or (256, 1024).
 int msu_mlp_fused_fwd(int dtype, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                       void* y, void* h, long M, int C, int Hd, void* stream) {
   if (!msu_is16(dtype) || !msu_mlp_fused_supported(C, Hd) || M < 0) return -2;

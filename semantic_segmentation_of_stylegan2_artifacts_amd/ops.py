@@ -1410,9 +1410,9 @@ mlp_train_calls = 0  # fused MLP launches storing H
 
 # the (C, hidden) shapes the fused MLP kernels are built for: msu_mlp_fused_supported restated
 # (Swin-T/S stage 0: csrc/mlp_fused.hip, weights resident in LDS; the rest -- Swin-T/S stage 1 and
-# Swin-B stage 0 -- csrc/mlp_s1.hip, weights streamed through an LDS ring; tests/test_capi.py
+# Swin-B stages 0 and 1 -- csrc/mlp_s1.hip, weights streamed through an LDS ring; tests/test_capi.py
 # checks the two agree), so fake kernels need no library
-MLP_KERNEL_SHAPES = ((96, 384), (192, 768), (128, 512))
+MLP_KERNEL_SHAPES = ((96, 384), (192, 768), (128, 512), (256, 1024))
 # MSU_MLP_S1=0: the streamed-weight shapes (all but the first) on the GEMM pair (A/B switch)
 _MLP_S1 = switches.on("MSU_MLP_S1")
 MLP_FUSED_SHAPES = MLP_KERNEL_SHAPES if _MLP_S1 else MLP_KERNEL_SHAPES[:1]

@@ -44,8 +44,9 @@ SWITCHES = {
     "MSU_CONV_WGRAD_BLOCKS": ("256", "persistent workgroups of the refine-conv weight gradient (one per CU by "
                               "default; fewer leave CUs to the main stream)", "DESIGN 7 (r04ac, r06)"),
     "MSU_MLP_S1": ("1", "0: the MLPs of the streamed-weight family (Swin-T/S stage 1, 192 -> 768, and Swin-B "
-                   "stage 0, 128 -> 512; training and no-grad) on the GEMM pair (H and GELU(H) stored) instead "
-                   "of the fused kernel streaming its weights through an LDS ring", "DESIGN 7 (r06e, r07a)"),
+                   "stages 0 and 1, 128 -> 512 and 256 -> 1024; training and no-grad) on the GEMM pair (H and "
+                   "GELU(H) stored) instead of the fused kernel streaming its weights through an LDS ring",
+                   "DESIGN 7 (r06e, r07a, r08a)"),
     "MSU_RES_HANDOFF": ("1", "0: a stage's first Swin block sums its input's two gradients (norm1 LayerNorm, norm2 "
                         "residual) with an ATen add instead of inside the LayerNorm backward", "DESIGN 7 (r06)"),
     "MSU_GRAPH": ("auto", "HIP-graph replay of the step: 1 / 0 / auto (replay when launch-bound)",
