@@ -155,11 +155,19 @@ int msu_conv3x3_fwd2(int dtype, int in_mode, const void* X, const void* Wt, cons
  * Wflip [9][Cin][roundup(Cout,32)], Wflip[t][ci][co] = W[co][ci][8-t]. */
 int msu_conv3x3_dgrad(int dtype, int out_mode, const void* dY, const void* Wflip, const void* S,
                       void* dX, int B, int H, int W, int Cin, int Cout, void* stream);
-/* 1 (default): the 96-channel refine-conv kernel takes its tiles from a device queue (per-stream
- * counter slot, reset by the launch's last workgroup), so workgroups that start late beside
- * the side stream's kernels take fewer tiles; 0: the static schedule (A/B switch MSU_CONV_DYN).
- * Returns the previous mode. */
+/* Mode bits of the refine convs; returns the previous mode.
+ * bit 0 (default on): the persistent refine-conv kernel (C = 96, 128) takes its tiles from a
+ * device queue (per-stream counter slot, reset by the launch's last workgroup), so workgroups
+ * that start late beside the side stream's kernels take fewer tiles; off: the static schedule
+ * (A/B switch MSU_CONV_DYN).
+ * bit 1 (default off): widths other than 96 take the generic kernels (weight gradient
+ * included) -- the A/B handle of the C = 128 kernels for tools and tests (no environment switch). */
 int msu_conv_mode(int mode);
+/* Which kernels serve a refine conv of (dtype, Cin, Cout): bit 0 set = forward / backward-data
+ * on a persistent LDS-DMA kernel, bit 1 set = the weight gradient on one; 0 = the generic
+ * kernels.  (bf16 | f16, 96, 96) and (bf16 | f16, 128, 128) are 3, fp32 is 0.  Does not depend
+ * on msu_conv_mode.  -2: unknown dtype or a non-positive width. */
+int msu_conv3x3_route(int dtype, int Cin, int Cout);
 long msu_conv3x3_wgrad_workspace(int nchunk, int Cin, int Cout, int dtype, int unused);
 /* dW [Cout][Cin][3][3] f32, db [Cout] f32 (deterministic partial-sum reduction). */
 int msu_conv3x3_wgrad(int dtype, int in_mode, const void* X, const void* dY, float* dW, float* db,

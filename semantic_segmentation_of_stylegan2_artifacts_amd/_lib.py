@@ -28,6 +28,7 @@ SIGNATURES = {
     "msu_reduce_rows": (I, [P, I, I, L, P, I, P]),
     "msu_tail_reduce_mode": (I, [I]),
     "msu_conv_mode": (I, [I]),
+    "msu_conv3x3_route": (I, [I, I, I]),
     "msu_head_fwd": (I, [I, P, P, P, P, P, P, P, L, I, F, P]),
     "msu_head_bwd": (I, [I, P, P, P, P, P, P, P, P, P, I, P, P, P, L, I, P]),
     "msu_head_bwd2": (I, [I, P, P, P, P, P, P, P, P, P, I, P, P, P, L, I, I, P]),

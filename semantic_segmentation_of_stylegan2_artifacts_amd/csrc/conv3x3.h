@@ -19,6 +19,9 @@
 #include "mfma_frag.h"
 #include "reduce.h"
 
+// msu_conv_mode bit 1 (conv3x3.hip), read by the weight-gradient dispatch as well
+int conv3x3_generic_wide();
+
 // MSU_EXP: ablation bits for timing experiments only (tools/build_exp.sh); 0 in every real build
 #ifndef MSU_EXP
 #define MSU_EXP 0
@@ -509,7 +512,7 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_v2_kernel(const bf16_t* __res
   }
 }
 
-// ------------------------------------------------------------------ 16-bit fwd, v3 (C = 96)
+// ------------------------------------------------------------------ 16-bit fwd / dgrad, v3 (C = 96, 128)
 // The v2 kernel (8 waves x one output row) spends as many LDS cycles as MFMA cycles: per tap
 // and wave 24 ds_read_b128 for 18 MFMAs, plus 24 KB of register-staged weight writes per tap.
 // v3 halves both per output pixel:
@@ -524,16 +527,106 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_v2_kernel(const bf16_t* __res
 //   * the next tile's halo is loaded into registers at tap 1 and written to LDS after tap 8.
 // Epilogue as v2 (bias, DUAL = GELU(Y) as a second output, GELU'(S) for the backward-data
 // launches with S prefetched at tap 7, 16-B stores after a permlane32 swap).
+//
+// C = 128 (Swin-B) is the same kernel at another width: every count below comes from V3W<C>.
+// Its 18 x 34 halo would be 157 KB, so a tile is 8 rows x 32 pixels (one row per wave; halo
+// [10][34][128] = 85 KB + two 32 KB weight images), and all of its launches run on 16x16x32
+// MFMA, where a weight fragment still feeds two MFMAs (the two 16-pixel halves of the row).
 constexpr int V3_HALO_TAP = 1;
-constexpr int SPRE = 12;  // GELU' operand loads per lane (dgrad)
-// ablation bit 1024: all of them at tap 7 (the round-5 placement; spilled halo registers)
+// ablation bit 1024: all GELU' operands at tap 7 (the round-5 placement; spilled halo registers)
 constexpr bool SP_AT7 = (MSU_EXP & 1024) != 0;
 
-MSU_DEV int swz(int p) { return (p >> 2) & 3; }
-// M16 (16x16x32 MFMA) fragment reads: 16 consecutive rows, chunk (lane >> 4) of a 4-chunk group;
-// the ds_read_b128 lane groups ({0-3, 12-15, 20-27}, ...) mix two chunks of 8 + 8 rows, which
-// (p >> 1) & 3 spreads over all 16 bank slots for ANY first row (checked exhaustively offline)
-template <bool M16> MSU_DEV int swzv(int p) { return M16 ? (p >> 1) & 3 : (p >> 2) & 3; }
+// Widths the kernel is built for (Cin == Cout == C) and everything derived from them.
+// TWV_: tile width in pixels; C = 128 fits 8 rows x 32 pixels (one row per wave) or 16 rows x
+// 16 pixels (two rows per wave) beside its weight images
+template <int C_, int TWV_ = 32>
+struct V3W {
+  static_assert(C_ == 96 || C_ == 128, "widths with a register plan and a conflict-free LDS image");
+  static_assert(TWV_ == 32 || (C_ == 128 && TWV_ == 16), "tile widths");
+  static constexpr int C = C_;
+  static constexpr int CH = C / 8;               // 16-B chunks per pixel / weight row
+  static constexpr int NW = 8;                   // waves
+  static constexpr int MT = C == 96 || TWV_ == 16 ? 2 : 1;  // image rows per wave
+  static constexpr int TH = NW * MT, TWV = TWV_, HWD = TWV + 2;
+  static constexpr int PT = TWV / 16;            // 16-pixel tiles per row (16x16x32 form)
+  static constexpr int HPIX = (TH + 2) * HWD;    // halo pixels (612 / 340 / 324)
+  static constexpr int NQ = C / 32;              // 32-channel groups: a lane's 16-B stores per pixel
+  static constexpr int NT32 = C / 32, KS32 = C / 16;  // 32x32x16 form: co tiles, k steps
+  static constexpr int NT16 = C / 16, KS16 = C / 32;  // 16x16x32 form
+  static constexpr int WIMG = C * C;             // elements of one tap's weight image
+  static constexpr int WINS = WIMG * 2 / 1024;   // 1-KB DMA wave-instructions per tap (18 / 32)
+  static constexpr int WPER = (WINS + NW - 1) / NW;   // per wave (<= 3 / 4)
+  static_assert(WINS * 1024 == WIMG * 2, "weight image in whole DMA instructions");
+  // GELU' operand loads per lane (dgrad): the first 32-channel group at tap 7, the rest at tap 8
+  static constexpr int SPRE = MT * PT * NQ;
+  static constexpr int SP7 = SP_AT7 ? SPRE : SPRE / NQ;
+  // halo + two weight images + bias + queue entry
+  static constexpr size_t LDS = sizeof(bf16_t) * ((size_t)HPIX * C + 2 * WIMG) + C * sizeof(float) + 16;
+  static_assert(LDS <= 160 * 1024, "LDS");
+  // the 32x32x16 form's k-step addressing assumes the 2-bit swizzle of the 192-B rows
+  template <bool M16> static constexpr bool form_ok = M16 || (C == 96 && TWV == 32);
+};
+
+// ---- LDS images.  Halo pixels and weight rows are unpadded [.][C]; the 16-B chunk c of row /
+// pixel p sits at chunk slot c ^ v3_swz(p).  The fragment reads, the halo stores and the DMA's
+// source permutation all go through v3_slot, and the asserts below check reads and DMA.
+//   C = 96 (192-B rows, two rows to three bank spans): (p >> 2) & 3 for the 32x32x16 form
+//   (a half-wave reads 32 consecutive rows, one chunk) and (p >> 1) & 3 for 16x16x32;
+//   C = 128: a row is one whole 256-B bank span, every row starts on bank 0, and a 2-bit
+//   swizzle leaves 16 rows on 4 columns.  (p & 7) << 1 moves the chunk's bits 1-3: a
+//   ds_read_b128 lane group holds 8 consecutive pixels with an even chunk and the 8 that follow
+//   with the next odd one, so each parity's 8 pixels take the 8 columns of that parity.
+#define V3_MAP __host__ __device__ __forceinline__ constexpr
+template <int C, bool M16> V3_MAP int v3_swz(int p) {
+  return C == 128 ? (p & 7) << 1 : M16 ? (p >> 1) & 3 : (p >> 2) & 3;
+}
+// element offset of chunk c of row / pixel p
+template <int C, bool M16> V3_MAP int v3_slot(int p, int c) { return p * C + ((c ^ v3_swz<C, M16>(p)) << 3); }
+// 16x16x32 form: k step ks of the fragment whose k step 0 is at `off` = v3_slot(p, lane >> 4).
+// The 2-bit swizzle stays inside a k step's four chunks (an immediate offset); the C = 128 one
+// does not, but rows are 128 elements, so the chunk's k-step bits flip in place.
+template <int C> V3_MAP int v3_kstep(int off, int ks) { return C == 128 ? off ^ (32 * ks) : off + 32 * ks; }
+// the weight DMA's 16-B piece q lands at byte 16 q of the image: row q / CH takes this chunk
+template <int C, bool M16> V3_MAP int v3_dma_chunk(int q) { return (q % (C / 8)) ^ v3_swz<C, M16>(q / (C / 8)); }
+
+// ds_read_b128 resolves bank conflicts within four groups of 16 lanes: lanes {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31} and the same plus 32.  Lane i (0 .. 15) of group g (0 .. 3):
+constexpr int v3_b128_lane(int g, int i) {
+  const int l = (g & 1) == 0 ? (i < 4 ? i : i < 8 ? i + 8 : i + 12) : (i < 8 ? i + 4 : i < 12 ? i + 8 : i + 16);
+  return l + 32 * (g >> 1);
+}
+// every 16x16x32 fragment read (16 consecutive rows / pixels from ANY first one -- the halo
+// reads start at (row + dy) * 34 + dx + 16 pt --, chunk 4 ks + (lane >> 4)) puts each group's
+// 16 lanes on 16 distinct 16-B bank columns
+template <int C>
+constexpr bool v3_reads_conflict_free() {
+  for (int p0 = 0; p0 < 64; ++p0)
+    for (int ks = 0; ks < V3W<C>::KS16; ++ks)
+      for (int g = 0; g < 4; ++g) {
+        unsigned cols = 0;
+        for (int i = 0; i < 16; ++i) {
+          const int lane = v3_b128_lane(g, i);
+          const int off = v3_kstep<C>(v3_slot<C, true>(p0 + (lane & 15), lane >> 4), ks);
+          cols |= 1u << ((off >> 3) & 15);
+        }
+        if (cols != 0xffffu) return false;
+      }
+  return true;
+}
+// the DMA writes the image the reads expect, and every k step reads its own four chunks
+template <int C, bool M16>
+constexpr bool v3_dma_writes_image() {
+  for (int q = 0; q < V3W<C>::WIMG / 8; ++q)
+    if (v3_slot<C, M16>(q / V3W<C>::CH, v3_dma_chunk<C, M16>(q)) != 8 * q) return false;
+  for (int p = 0; p < 64; ++p)
+    for (int ks = 0; ks < V3W<C>::KS16; ++ks)
+      for (int g4 = 0; g4 < 4; ++g4)
+        if (v3_kstep<C>(v3_slot<C, true>(p, g4), ks) != v3_slot<C, true>(p, 4 * ks + g4)) return false;
+  return true;
+}
+static_assert(v3_reads_conflict_free<96>() && v3_reads_conflict_free<128>(), "halo / weight image: bank conflicts");
+static_assert(v3_dma_writes_image<96, true>() && v3_dma_writes_image<96, false>() && v3_dma_writes_image<128, true>(),
+              "weight image: DMA and reads disagree");
 
 // SPREAD: the next tile's halo loads are issued in seven parts at taps 1..7 (each part issued
 // after that tap's weight DMA, so it only has to land two taps later) instead of all at tap 1,
@@ -543,35 +636,39 @@ MSU_DEV constexpr int halo_part_lo(int t, int nhc) { return (t - 1) * nhc / 7; }
 // Tile queue (tq, common.h): a workgroup takes its first tile statically (blockIdx.x) and claims
 // every further one from counter 0, one tile ahead (the next tile's halo and weight prefetch
 // need its index from tap 1 on).  Results do not depend on which workgroup computes a tile.
-template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL, bool SPREAD, bool M16>
+template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL, bool SPREAD, bool M16,
+          int CW = 96, int TWW = 32>
 __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restrict__ X,
                                                          const bf16_t* __restrict__ Wt,
                                                          const float* __restrict__ bias,
                                                          const bf16_t* __restrict__ S,
                                                          bf16_t* __restrict__ Y, bf16_t* __restrict__ Y2,
                                                          ConvGeom g, int ntiles, int* __restrict__ tq) {
-  constexpr int C = 96, CH = 12, NW = 8, MT = 2, TH = NW * MT, TWV = 32, HWD = TWV + 2;
-  constexpr int HPIX = (TH + 2) * HWD;  // 612 halo pixels
+  using G = V3W<CW, TWW>;
+  static_assert(G::template form_ok<M16>, "the 32x32x16 form is built for C = 96 only");
+  constexpr int C = G::C, CH = G::CH, NW = G::NW, MT = G::MT, TH = G::TH, TWV = G::TWV, HWD = G::HWD;
+  constexpr int HPIX = G::HPIX;
   (void)HPIX;
+  constexpr int PT = G::PT, NQ = G::NQ, NT32 = G::NT32, KS32 = G::KS32, NT16 = G::NT16, KS16 = G::KS16;
   constexpr int NTHR = 64 * NW;
   constexpr int PSTEP = NTHR / CH;                // halo pixels per staging round (one channel
-                                                  // chunk per thread: thread t stages chunk t % 12)
+                                                  // chunk per thread: thread t stages chunk t % CH)
   constexpr int NHC = (HPIX + PSTEP - 1) / PSTEP;  // staging rounds
-  constexpr int WIMG = C * C;                   // elements of one tap's weight image
-  constexpr int WINS = WIMG * 2 / 1024;         // 18 DMA wave-instructions per tap
-  constexpr int WPER = (WINS + NW - 1) / NW;    // <= 3 per wave
-  static_assert(WINS * 1024 == WIMG * 2, "weight image in whole DMA instructions");
+  constexpr int WIMG = G::WIMG;                 // elements of one tap's weight image
+  constexpr int WINS = G::WINS;                 // DMA wave-instructions per tap
+  constexpr int WPER = G::WPER;                 // per wave
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   bf16_t* sX = reinterpret_cast<bf16_t*>(smem_raw);
-  bf16_t* sW = sX + HPIX * C;  // [2][96][96]
-  float* sB = reinterpret_cast<float*>(sW + 2 * WIMG);  // [96] bias (BIAS)
+  bf16_t* sW = sX + HPIX * C;  // [2][C][C]
+  float* sB = reinterpret_cast<float*>(sW + 2 * WIMG);  // [C] bias (BIAS)
   int* sQ = reinterpret_cast<int*>(sB + C);              // the claimed next tile (tq)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tiles_x = (g.W + TWV - 1) / TWV, tiles_y = (g.H + TH - 1) / TH;
   // output stores of a whole tile, per wave (16-B stores; DUAL: two per output chunk)
-  constexpr int EST = MT * 6 * (DUAL ? 2 : 1);
+  constexpr int EST = MT * PT * NQ * (DUAL ? 2 : 1);
+  static_assert(WPER + EST < 64, "tap 0's counted wait fits vmcnt");
   const int per_img = tiles_x * tiles_y;
 
   auto coords = [&](int tile, int& b, int& y0, int& x0) {
@@ -581,7 +678,7 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
     x0 = (r - (r / tiles_x) * tiles_x) * TWV;
   };
   u32x4 hr[NHC];
-  // Halo staging: thread t < 12 * PSTEP owns channel chunk t % 12 of pixels t / 12 + PSTEP * c
+  // Halo staging: thread t < CH * PSTEP owns channel chunk t % CH of pixels t / CH + PSTEP * c
   // (c = 0 .. NHC-1); the pixel's (row, col) advance incrementally, so a chunk costs a few adds
   // and one address multiply instead of the divisions of a flat chunk index
   // rounds [c0, c1) of this thread's share of tile `tile`'s halo -> registers
@@ -619,23 +716,22 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
     int p = t / CH;
 #pragma unroll
     for (int c = 0; c < NHC; ++c) {
-      if (hact && p < HPIX) *reinterpret_cast<u32x4*>(sX + p * C + ((hch ^ swzv<M16>(p)) << 3)) = hr[c];
+      if (hact && p < HPIX) *reinterpret_cast<u32x4*>(sX + v3_slot<C, M16>(p, hch)) = hr[c];
       p += PSTEP;
     }
   };
   // this wave's share of the DMA of tap `tap`'s weight image into buffer `buf`
-  // this wave's share of the DMA of tap `tap`'s weight image into buffer `buf`
   auto dma_w = [&](int tap, int buf) {
     const bf16_t* src = Wt + (long)tap * WIMG;
     bf16_t* dst = sW + buf * WIMG;
-    // piece r of this wave is slot q = 64 (wave + NW r) + lane: row q / 12, chunk q % 12,
+    // piece r of this wave is slot q = 64 (wave + NW r) + lane: row q / CH, chunk q % CH,
     // advanced incrementally from r = 0 (one division per call)
     const int q0 = 64 * wave + opaque(lane);
     int row = q0 / CH, pos = q0 - (q0 / CH) * CH;
 #pragma unroll
     for (int r = 0; r < WPER; ++r) {
       const int k = wave + NW * r;
-      if (WINS % NW == 0 || k < WINS) glds16((MSU_EXP & 512) ? src + lane * 8 : src + row * C + ((pos ^ swzv<M16>(row)) << 3), dst + 512 * k);
+      if (WINS % NW == 0 || k < WINS) glds16((MSU_EXP & 512) ? src + lane * 8 : src + v3_slot<C, M16>(row, pos), dst + 512 * k);
       pos += (64 * NW) % CH;
       row += (64 * NW) / CH;
       if (pos >= CH) {
@@ -680,11 +776,11 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
   // lane chunk offsets (elements) of k steps with ks even / odd, for row / pixel swizzle sw:
   // chunk 2ks + h -> 4 (ks >> 1) + ((2 (ks & 1) + h) ^ sw)
   auto koff = [&](int sw, int odd) { return ((2 * odd + h) ^ sw) << 3; };
-  const int wsw = swz(xl);  // weight rows 32n + xl
+  const int wsw = v3_swz<C, false>(xl);  // weight rows 32n + xl
   const int wk0 = xl * C + koff(wsw, 0), wk1 = xl * C + koff(wsw, 1);
   // M16: lane l reads row (l & 15) of a 16-row fragment, chunk 4 ks + (l >> 4)
   const int l15 = lane & 15, g4 = lane >> 4;
-  const int wk16 = l15 * C + ((g4 ^ swzv<true>(l15)) << 3);  // weight rows 16n + l15
+  const int wk16 = v3_slot<C, true>(l15, g4);  // weight rows 16n + l15, k step 0
 
   for (;;) {
     int nn = 0;  // thread 0 (tq): the tile after next, claimed at tap 1
@@ -693,23 +789,23 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
     const int xo = x0 + xl;
     // accumulators: 32x32 tiles [row m][co tile n] (!M16) or 16x16 tiles [row m][pixel tile
     // pt][co tile n] (M16); the other form is a 1-element placeholder
-    f32x16 acc[M16 ? 1 : MT][M16 ? 1 : 3];
-    f32x4 acc4[M16 ? MT : 1][M16 ? 2 : 1][M16 ? 6 : 1];
+    f32x16 acc[M16 ? 1 : MT][M16 ? 1 : NT32];
+    f32x4 acc4[M16 ? MT : 1][M16 ? PT : 1][M16 ? NT16 : 1];
     if constexpr (M16) {
 #pragma unroll
       for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int pt = 0; pt < 2; ++pt)
+        for (int pt = 0; pt < PT; ++pt)
 #pragma unroll
-          for (int n = 0; n < 6; ++n) acc4[m][pt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int n = 0; n < NT16; ++n) acc4[m][pt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     } else {
 #pragma unroll
       for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int n = 0; n < 3; ++n) acc[m][n] = f32x16{0};
+        for (int n = 0; n < NT32; ++n) acc[m][n] = f32x16{0};
     }
-    // dgrad GELU' operands: 12 16-B pieces per lane in both forms
-    u32x4 sp[OUT_GGRAD ? MT : 1][OUT_GGRAD ? (M16 ? 2 : 3) : 1][OUT_GGRAD ? (M16 ? 3 : 2) : 1];
+    // dgrad GELU' operands: SPRE 16-B pieces per lane in both forms
+    u32x4 sp[OUT_GGRAD ? MT : 1][OUT_GGRAD ? (M16 ? PT : NQ) : 1][OUT_GGRAD ? (M16 ? NQ : 2) : 1];
 
     static_for([&](auto TAP) {
       constexpr int tap = decltype(TAP)::value;
@@ -721,7 +817,7 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
       constexpr int hprev = SPREAD ? (tap >= 2 ? halo_part_lo(tap, NHC) - halo_part_lo(tap - 1, NHC) : 0)
                                    : (tap == V3_HALO_TAP + 1 ? NHC : 0);
       // (only a third of them are issued at tap 7, see load_sp / load_sp16)
-      constexpr int sprev = (OUT_GGRAD && tap == 8) ? (SP_AT7 ? SPRE : SPRE / 3) : 0;
+      constexpr int sprev = (OUT_GGRAD && tap == 8) ? G::SP7 : 0;
       if constexpr (tap == 0) {
         // W(0) landed (DMA'd at the previous tile's tap 8); W(1) and the previous tile's output
         // stores, issued after it in that epilogue, may stay in flight
@@ -784,7 +880,7 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
       // dgrad, 16 x 16 form: the operands of channel group q (32 q .. 32 q + 31) of rows m
       auto load_sp16 = [&](int m, int y, int q) __attribute__((always_inline)) {
 #pragma unroll
-        for (int pt = 0; pt < 2; ++pt) {
+        for (int pt = 0; pt < PT; ++pt) {
           const int xs = min(x0 + 16 * pt + l15, g.W - 1);
           sp[m][pt][q] = *reinterpret_cast<const u32x4*>(S + pix_off32<OUT_D2S>(b, y, xs, g.H, g.W, C) + 32 * q +
                                                          16 * (g4 & 1) + 8 * (g4 >> 1));
@@ -794,74 +890,79 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
         // dgrad: the pre-activation S of this tile's outputs for the GELU' epilogue
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          const int y = min(y0 + 2 * wave + m, g.H - 1);
+          const int y = min(y0 + MT * wave + m, g.H - 1);
           if constexpr (M16) {
             load_sp16(m, y, 0);
             if constexpr (SP_AT7) {
-              load_sp16(m, y, 1);
-              load_sp16(m, y, 2);
+#pragma unroll
+              for (int q = 1; q < NQ; ++q) load_sp16(m, y, q);
             }
           } else {
             load_sp(m, y, 0);
             if constexpr (SP_AT7) {
-              load_sp(m, y, 1);
-              load_sp(m, y, 2);
+#pragma unroll
+              for (int q = 1; q < NQ; ++q) load_sp(m, y, q);
             }
           }
         }
       }
       if constexpr (M16) {
         // fragment lane offsets of this tap: X rows 2w + m + dy, pixels dx + 16 pt + l15
-        int xq[MT][2];
+        int xq[MT][PT];
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-          for (int pt = 0; pt < 2; ++pt) {
-            const int p = opaque((2 * wave + m + dy) * HWD + dx + 16 * pt) + l15;
-            xq[m][pt] = p * C + ((g4 ^ swzv<true>(p)) << 3);
+          for (int pt = 0; pt < PT; ++pt) {
+            const int p = opaque((MT * wave + m + dy) * HWD + dx + 16 * pt) + l15;
+            xq[m][pt] = v3_slot<C, true>(p, g4);
           }
-        // groups (ks, m) in sequence: a group's two X fragments (pixel tiles) feed 12 MFMAs, the
+        // groups (ks, fragment pair) in sequence; the MT * PT X fragments of a k step are numbered
+        // PT * m + pt and paired in that order (a row's two pixel tiles, or the two rows of a
+        // 16-pixel tile): a group's two X fragments feed 2 NT16 MFMAs, the
         // next group's are read at its start; weight fragments in a ring of two, one co tile
         // ahead (re-read per row m: 16 reads per 24 MFMAs, within the LDS budget of 16x16x32
         // gaps; double-buffering all four X fragments of a k step spilled)
         bf16x8 xb[2][2], wf[2];
+        constexpr int GPK = MT * PT / 2;  // groups per k step
         auto read_x = [&](auto GI, int set) __attribute__((always_inline)) {
-          constexpr int gi = decltype(GI)::value, ks = gi / MT, m = gi % MT;
+          constexpr int gi = decltype(GI)::value, ks = gi / GPK, f0 = 2 * (gi % GPK);
 #pragma unroll
-          for (int pt = 0; pt < 2; ++pt) xb[set][pt] = *reinterpret_cast<const bf16x8*>(sX + xq[m][pt] + 32 * ks);
+          for (int j = 0; j < 2; ++j)
+            xb[set][j] = *reinterpret_cast<const bf16x8*>(sX + v3_kstep<C>(xq[(f0 + j) / PT][(f0 + j) % PT], ks));
         };
         auto read_w = [&](auto GI, int n) __attribute__((always_inline)) -> bf16x8 {
-          constexpr int ks = decltype(GI)::value / MT;
-          return *reinterpret_cast<const bf16x8*>(wcur + 16 * n * C + wk16 + 32 * ks);
+          constexpr int ks = decltype(GI)::value / GPK;
+          return *reinterpret_cast<const bf16x8*>(wcur + 16 * n * C + v3_kstep<C>(wk16, ks));
         };
         read_x(IC<0>{}, 0);
         wf[0] = read_w(IC<0>{}, 0);
         static_for([&](auto GI) {
-          constexpr int gi = decltype(GI)::value, m = gi % MT;
+          constexpr int gi = decltype(GI)::value, f0 = 2 * (gi % GPK);
           constexpr int cur = gi & 1;
-          if constexpr (gi + 1 < 3 * MT) read_x(IC<gi + 1>{}, cur ^ 1);
+          if constexpr (gi + 1 < KS16 * GPK) read_x(IC<gi + 1>{}, cur ^ 1);
           static_for([&](auto NI) {
             constexpr int n = decltype(NI)::value;
-            constexpr int j = 6 * gi + n;  // weight fragment sequence number: register set j & 1
-            if constexpr (n < 5) wf[(j + 1) & 1] = read_w(IC<gi>{}, n + 1);
-            else if constexpr (gi + 1 < 3 * MT) wf[(j + 1) & 1] = read_w(IC<gi + 1>{}, 0);
+            constexpr int j = NT16 * gi + n;  // weight fragment sequence number: register set j & 1
+            if constexpr (n < NT16 - 1) wf[(j + 1) & 1] = read_w(IC<gi>{}, n + 1);
+            else if constexpr (gi + 1 < KS16 * GPK) wf[(j + 1) & 1] = read_w(IC<gi + 1>{}, 0);
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt) {
-              if constexpr (MSU_EXP & 128) asm volatile("" ::"v"(wf[j & 1]), "v"(xb[cur][pt]));  // ablation: no MFMA
-              else acc4[m][pt][n] = Fmt16<T>::mma16(wf[j & 1], xb[cur][pt], acc4[m][pt][n]);
+            for (int jx = 0; jx < 2; ++jx) {
+              const int m = (f0 + jx) / PT, pt = (f0 + jx) % PT;
+              if constexpr (MSU_EXP & 128) asm volatile("" ::"v"(wf[j & 1]), "v"(xb[cur][jx]));  // ablation: no MFMA
+              else acc4[m][pt][n] = Fmt16<T>::mma16(wf[j & 1], xb[cur][jx], acc4[m][pt][n]);
             }
-          }, std::make_integer_sequence<int, 6>{});
+          }, std::make_integer_sequence<int, NT16>{});
           __builtin_amdgcn_sched_barrier(0);
-        }, std::make_integer_sequence<int, 3 * MT>{});
+        }, std::make_integer_sequence<int, KS16 * GPK>{});
       } else {
         // fragment lane offsets of this tap: X rows 2w + m + dy, pixels dx + xl
         // (recomputed per tap through opaque(): hoisted, the nine taps' offsets would pin 36 VGPRs)
         int xo0[MT], xo1[MT];
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          const int p = opaque((2 * wave + m + dy) * HWD + dx) + xl;
-          xo0[m] = p * C + koff(swz(p), 0);
-          xo1[m] = p * C + koff(swz(p), 1);
+          const int p = opaque((MT * wave + m + dy) * HWD + dx) + xl;
+          xo0[m] = p * C + koff(v3_swz<C, false>(p), 0);
+          xo1[m] = p * C + koff(v3_swz<C, false>(p), 1);
         }
         // X fragments double buffered (k step ks + 1 read before the MFMAs of ks); each weight
         // fragment is read one co tile ahead of its two MFMAs (registers: the halo prefetch
@@ -884,37 +985,35 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
         static_for([&](auto KSI) {
           constexpr int ks = decltype(KSI)::value;
           constexpr int cur = ks & 1;
-          if constexpr (ks + 1 < 6) read_x(IC<ks + 1>{}, cur ^ 1);
+          if constexpr (ks + 1 < KS32) read_x(IC<ks + 1>{}, cur ^ 1);
           static_for([&](auto NI) {
             constexpr int n = decltype(NI)::value;
-            constexpr int j = 3 * ks + n;  // weight fragment sequence number: register set j & 1
+            constexpr int j = NT32 * ks + n;  // weight fragment sequence number: register set j & 1
             // (reading it two groups ahead in a ring of three measured no faster and spills the dgrad)
-            if constexpr (n < 2) wf[(j + 1) & 1] = read_w(IC<ks>{}, n + 1);
-            else if constexpr (ks + 1 < 6) wf[(j + 1) & 1] = read_w(IC<ks + 1>{}, 0);
+            if constexpr (n < NT32 - 1) wf[(j + 1) & 1] = read_w(IC<ks>{}, n + 1);
+            else if constexpr (ks + 1 < KS32) wf[(j + 1) & 1] = read_w(IC<ks + 1>{}, 0);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
               if constexpr (MSU_EXP & 128) asm volatile("" ::"v"(wf[j & 1]), "v"(xa[cur][m]));  // ablation: no MFMA
               else acc[m][n] = Fmt16<T>::mma32(wf[j & 1], xa[cur][m], acc[m][n]);
             }
-          }, std::make_integer_sequence<int, 3>{});
+          }, std::make_integer_sequence<int, NT32>{});
           __builtin_amdgcn_sched_barrier(0);
-        }, std::make_integer_sequence<int, 6>{});
+        }, std::make_integer_sequence<int, KS32>{});
       }
       if constexpr (tap == 8) {
         if constexpr (OUT_GGRAD && !SP_AT7) {
-          // co tiles 1-2's GELU' operands after the last MFMAs: held through taps 7-8 beside the
+          // the other 32-channel groups' GELU' operands after the last MFMAs: held through taps 7-8 beside the
           // full halo prefetch they pushed the kernel past 256 VGPRs (halo registers spilled,
           // each spill store a vmcnt(0) at tap 1); their latency is exposed at the epilogue's
           // wait instead
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
-            const int y = min(y0 + 2 * wave + m, g.H - 1);
-            if constexpr (M16) {
-              load_sp16(m, y, 1);
-              load_sp16(m, y, 2);
-            } else {
-              load_sp(m, y, 1);
-              load_sp(m, y, 2);
+            const int y = min(y0 + MT * wave + m, g.H - 1);
+#pragma unroll
+            for (int q = 1; q < NQ; ++q) {
+              if constexpr (M16) load_sp16(m, y, q);
+              else load_sp(m, y, q);
             }
           }
         }
@@ -937,9 +1036,9 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-          for (int n = 0; n < (M16 ? 2 : 3); ++n)
+          for (int n = 0; n < (M16 ? PT : NQ); ++n)
 #pragma unroll
-            for (int pp = 0; pp < (M16 ? 3 : 2); ++pp) vreg_pin(sp[m][n][pp]);
+            for (int pp = 0; pp < (M16 ? NQ : 2); ++pp) vreg_pin(sp[m][n][pp]);
       }
       w1_early = next < ntiles;
       st_full = w1_early && x0 + TWV <= g.W && y0 + TH <= g.H;
@@ -951,21 +1050,21 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
       // of co tiles (2q, 2q + 1) gives every lane 8 consecutive channels co8 .. co8 + 7 with
       // co8 = 16 (2q + (g4 & 1)) + 8 (g4 >> 1) (lanes l, l ^ 16 share the pixel)
       const int cofs = 16 * (g4 & 1) + 8 * (g4 >> 1);
-      float4 bq[3][2];
+      float4 bq[NQ][2];
       if constexpr (BIAS) {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int q = 0; q < NQ; ++q) {
           bq[q][0] = *reinterpret_cast<const float4*>(sB + 32 * q + cofs);
           bq[q][1] = *reinterpret_cast<const float4*>(sB + 32 * q + cofs + 4);
         }
       }
       epi_start();
 #pragma unroll
-      for (int pt = 0; pt < 2; ++pt) {
+      for (int pt = 0; pt < PT; ++pt) {
         const int px = x0 + 16 * pt + l15;
         if (px >= g.W) continue;  // lanes l and l ^ 16 agree
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int q = 0; q < NQ; ++q) {
           float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
           if constexpr (BIAS) {
             const float4 t0 = bq[q][0], t1 = bq[q][1];
@@ -974,7 +1073,7 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
           }
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
-            const int y = y0 + 2 * wave + m;
+            const int y = y0 + MT * wave + m;
             float v[8];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1006,10 +1105,10 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
     // permlane32 swap gives lane l < 32 channels 32n + 16pp + 0..7 and l + 32 the next 8
     // bias columns of this lane's 6 store groups, loaded together: one wait, not one per
     // store group behind the previous group's stores
-    float4 bq[3][2][2];
+    float4 bq[NT32][2][2];
     if constexpr (BIAS) {
 #pragma unroll
-      for (int n = 0; n < 3; ++n)
+      for (int n = 0; n < NT32; ++n)
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
           const int co = 32 * n + 16 * pp + 8 * h;
@@ -1020,7 +1119,7 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
     epi_start();
     if (xo < g.W) {
 #pragma unroll
-      for (int n = 0; n < 3; ++n)
+      for (int n = 0; n < NT32; ++n)
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
           const int co = 32 * n + 16 * pp + 8 * h;
@@ -1032,7 +1131,7 @@ __global__ void __launch_bounds__(512) conv3x3_v3_kernel(const bf16_t* __restric
           }
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
-            const int y = y0 + 2 * wave + m;
+            const int y = y0 + MT * wave + m;
             float v[8];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1364,6 +1463,210 @@ __global__ void __launch_bounds__(768) conv3x3_wgrad_v2_kernel(const bf16_t* __r
   }
 }
 
+// ------------------------------------------------------------------ 16-bit wgrad, v2 at C = 128
+// conv3x3_wgrad_v2_kernel's plan at the Swin-B width.  All nine taps of 128 x 128 are 576 KB of
+// f32 accumulators, more than a CU's register file, so a workgroup owns one HALF of the output
+// channels: block 2 s + h takes the tiles of pixel share s (s, s + nshare, ...) and co
+// 64 h .. 64 h + 63.  Same 12 waves (dy x co half of the block's 64 x ci half), each 3 dx x
+// 2 co tiles x 4 ci tiles = 96 accumulator registers; the X halo [6 x 34][128] sits at a pixel
+// stride of 136 elements (17 slots), the block's dY half-tile [128][64] at 72 (9 slots): pixels
+// two apart are 136 / 72 dwords = 8 mod 64 banks apart in both images, i.e. the 8 pixels of one
+// parity that a half-wave's k-strided read touches sit on distinct 32-B bank spans, as at 96.
+// Each X band is staged by the two blocks of a share.  Partials: chunk s of [chunk][dy][co][dx][ci] + db[chunk][co], each block
+// writing its 64 co rows -- the layout and the deterministic reduction are unchanged, over
+// nshare chunks.
+template <typename T, bool IN_D2S, bool IN_GELU>
+__global__ void __launch_bounds__(768) conv3x3_wgrad_v2h_kernel(const bf16_t* __restrict__ X,
+                                                                const bf16_t* __restrict__ DY,
+                                                                float* __restrict__ part,
+                                                                float* __restrict__ dbpart, ConvGeom g,
+                                                                int ntiles) {
+  constexpr int C = 128, COB = 64, TH = 4, TWV = 32, NW = 12;
+  constexpr int NI = COB / 32, NJ = C / 32;  // 16-wide co / ci tiles per wave
+  constexpr int PSX = C + 8, SLX = PSX / 8;  // X image: pixel stride, 16-B slots per pixel (16 + 1 pad)
+  constexpr int PSD = COB + 8, SLD = PSD / 8;  // dY image (8 + 1 pad)
+  constexpr int HWD = TWV + 2;
+  constexpr int HPIX = (TH + 2) * HWD;       // 204 halo pixels
+  constexpr int DPIX = TH * TWV;             // 128 dY pixels
+  constexpr int XSLOT = HPIX * SLX;          // slots of the X image; the dY image follows
+  constexpr int NSLOT = XSLOT + DPIX * SLD;
+  constexpr int NINS = (NSLOT + 63) / 64;    // DMA wave-instructions per tile
+  constexpr int PER_WAVE = (NINS + NW - 1) / NW;
+  constexpr int BUF = NINS * 64 * 8;         // elements per LDS buffer (covers the overrun)
+  static_assert(2 * BUF * sizeof(bf16_t) <= 160 * 1024, "LDS");
+  static_assert(2 * ((3 * HWD + 2) * PSX + 16 * (NJ - 1) + 32 * PSX) < 65536, "fragment read offsets are immediates");
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef __attribute__((address_space(1))) void glb_void;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  bf16_t* lds = reinterpret_cast<bf16_t*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int dy = wave >> 2, coh = (wave >> 1) & 1, cih = wave & 1;
+  const int share = blockIdx.x >> 1, half = blockIdx.x & 1, nshare = gridDim.x >> 1;
+  const int tiles_x = (g.W + TWV - 1) / TWV, tiles_y = (g.H + TH - 1) / TH;
+  const int per_img = tiles_x * tiles_y;
+
+  auto coords = [&](int tile, int& b, int& y0, int& x0) {
+    b = tile / per_img;
+    const int r = tile - b * per_img;
+    y0 = (r / tiles_x) * TH;
+    x0 = (r - (r / tiles_x) * tiles_x) * TWV;
+  };
+  // issue this wave's DMAs of tile `tile` into buffer `buf`
+  auto stage = [&](int tile, int buf) __attribute__((always_inline)) {
+    int b, y0, x0;
+    coords(tile, b, y0, x0);
+    const int ln = opaque(lane);
+#pragma unroll
+    for (int r = 0; r < PER_WAVE; ++r) {
+      const int k = wave + NW * r;
+      if (k < NINS) {
+        const int s = 64 * k + ln;
+        const void* src = zero_src(s);
+        if (s < XSLOT) {
+          const int pix = s / SLX, ch0 = s - (s / SLX) * SLX;
+          const int ch = ch0 < SLX - 1 ? ch0 : 0;  // pad slot: re-read chunk 0 of the pixel
+          const int row = pix / HWD, col = pix - (pix / HWD) * HWD;
+          const int y = y0 - 1 + row, x = x0 - 1 + col;
+          if (y >= 0 && y < g.H && x >= 0 && x < g.W) src = X + pix_off32<IN_D2S>(b, y, x, g.H, g.W, C) + ch * 8;
+        } else if (s < NSLOT) {
+          const int t = s - XSLOT;
+          const int dp = t / SLD, ch0 = t - (t / SLD) * SLD;
+          const int ch = ch0 < SLD - 1 ? ch0 : 0;
+          const int y = y0 + dp / TWV, x = x0 + dp % TWV;
+          if (y < g.H && x < g.W) src = DY + pix_off32<false>(b, y, x, g.H, g.W, C) + COB * half + ch * 8;
+        }
+        __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(lds + buf * BUF + 64 * 8 * k), 16, 0, 0);
+      }
+    }
+  };
+  // after this wave's DMAs landed: GELU the halo slots it wrote, in place
+  auto gelu_own = [&](int buf) __attribute__((always_inline)) {
+    if constexpr (IN_GELU) {
+      const int ln = opaque(lane);
+#pragma unroll
+      for (int r = 0; r < PER_WAVE; ++r) {
+        const int k = wave + NW * r;
+        const int s = 64 * k + ln;
+        if (k < NINS && s < XSLOT && s % SLX < SLX - 1) {
+          u32x4* p = reinterpret_cast<u32x4*>(lds + buf * BUF + 8 * s);
+          *p = gelu8<T>(*p);
+        }
+      }
+    }
+  };
+
+  f32x4 acc[3][NI][NJ];  // [dx][co tile][ci tile]
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[d][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float dbacc[2] = {0.f, 0.f};
+  // bias gradient: threads 0 .. 511 = 16 pixel groups x 32 channel pairs
+  const bool dbon = tid < 16 * (COB / 2);
+  const int dbc = 2 * (tid % (COB / 2)), dbg = dbon ? tid / (COB / 2) : 0;
+
+  int tile = share;
+  int cur = 0;
+  if (tile < ntiles) {
+    stage(tile, 0);
+    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) & lgkmcnt(0)
+    gelu_own(0);
+  }
+  __syncthreads();
+  for (; tile < ntiles; tile += nshare) {
+    const int next = tile + nshare;
+    if (next < ntiles) stage(next, cur ^ 1);
+    const bf16_t* sX = lds + cur * BUF;
+    const bf16_t* sD = sX + HPIX * PSX;
+    // All LDS reads of the tile are untracked (inline asm): a compiler-visible ds_read would
+    // be preceded by vmcnt(0) for the next tile's pending LDS-DMA and serialise the two.
+    {
+      const uint32_t ba = lds_u32(sD + dbg * PSD + dbc);
+      uint32_t v[DPIX / 16];
+      unroll_for<DPIX / 16>([&](auto P) {
+        v[decltype(P)::value] = ds_b32_untracked<2 * 16 * PSD * decltype(P)::value>(ba);
+      });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int p = 0; p < DPIX / 16; ++p) {
+        vreg_pin(v[p]);
+        dbacc[0] += Fmt16<T>::lo(v[p]);
+        dbacc[1] += Fmt16<T>::hi(v[p]);
+      }
+    }
+    // lane part of a k-strided fragment read (as conv3x3_wgrad_v2_kernel): pixels
+    // 2(4g + q) + half-wave, columns 4(lane&3); everything else is an immediate offset
+    const int lpix = 2 * (4 * ((lane >> 4) & 1) + ((lane & 15) >> 2)) + (lane >> 5);
+    const int lx = opaque(lpix * PSX + 4 * (lane & 3)), ld = opaque(lpix * PSD + 4 * (lane & 3));
+    const uint32_t xa = lds_u32(sX + lx + dy * HWD * PSX + (C / 2) * cih);
+    const uint32_t da = lds_u32(sD + ld + (COB / 2) * coh);
+    unroll_for<TH>([&](auto R) {
+      constexpr int r = decltype(R)::value;
+      // the dY fragments of row r serve all three dx
+      bf16x8 af[NI];
+      unroll_for<NI>([&](auto I) {
+        constexpr int o = 2 * (r * TWV * PSD + 16 * decltype(I)::value);
+        af[decltype(I)::value] = tr8_untracked<o, o + 32 * PSD>(da);
+      });
+      unroll_for<3>([&](auto D) {
+        constexpr int d = decltype(D)::value;
+        bf16x8 bf[NJ];
+        unroll_for<NJ>([&](auto J) {
+          constexpr int o = 2 * ((r * HWD + d) * PSX + 16 * decltype(J)::value);
+          bf[decltype(J)::value] = tr8_untracked<o, o + 32 * PSX>(xa);
+        });
+        if constexpr (d == 0)
+          lds_wait_tie<0>(bf[0], bf[1], bf[2], bf[3], af[0], af[1]);
+        else
+          lds_wait_tie<0>(bf[0], bf[1], bf[2], bf[3]);
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) acc[d][i][j] = Fmt16<T>::mma16(af[i], bf[j], acc[d][i][j]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    });
+    if (next < ntiles) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      gelu_own(cur ^ 1);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  // partial [share][dy][co][dx][ci]: lane holds co = co0 + 4(lane>>4) + r, ci = ci0 + (lane&15)
+  float* out = part + ((long)share * 3 + dy) * (long)C * 3 * C;
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = COB * half + (COB / 2) * coh + 16 * i + 4 * (lane >> 4) + r;
+          const int ci = (C / 2) * cih + 16 * j + (lane & 15);
+          out[((long)co * 3 + d) * C + ci] = acc[d][i][j][r];
+        }
+  // bias partial: reduce the 16 pixel groups through LDS
+  float* red = reinterpret_cast<float*>(smem_raw);
+  __syncthreads();
+  if (dbon) {
+    red[dbg * COB + dbc] = dbacc[0];
+    red[dbg * COB + dbc + 1] = dbacc[1];
+  }
+  __syncthreads();
+  if (tid < COB) {
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sum += red[q * COB + tid];
+    dbpart[(long)share * C + COB * half + tid] = sum;
+  }
+}
+
 // chunk-summed partial [dy][co][dx][ci] -> dW[co][ci][3][3] (torch Conv2d layout)
 __global__ void __launch_bounds__(256) wgrad_permute_kernel(const float* __restrict__ sum, int Cout, int Cin,
                                                             int CinP, float* __restrict__ dW, int accumulate) {
@@ -1414,6 +1717,9 @@ int launch_conv(const ConvGeom& g, const T* X, const T* Wt, const float* bias, c
 // msu_conv_mode bit 0 (default on; A/B switch MSU_CONV_DYN): conv3x3_v3_kernel takes tiles
 // from the per-stream queue slot instead of the static blockIdx.x + k * gridDim.x schedule
 int g_conv_dyn = 1;
+// msu_conv_mode bit 1 (default off; the A/B handle of tools and tests, no environment switch):
+// widths other than 96 take the generic kernels
+int g_conv_generic_wide = 0;
 
 int num_cus() {
   static int n = 0;
@@ -1447,22 +1753,24 @@ int launch_v2(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float*
   return MSU_CHECK_LAUNCH();
 }
 
-template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL, bool SPREAD, bool M16>
+template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL, bool SPREAD, bool M16,
+          int CW = 96, int TWW = 32>
 int launch_v3s(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S, bf16_t* Y,
                bf16_t* Y2, hipStream_t st) {
-  constexpr size_t lds = sizeof(bf16_t) * ((size_t)18 * 34 * 96 + 2 * 96 * 96) + 96 * sizeof(float) + 16;  // + bias, queue
-  static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv3x3_v3_kernel<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, SPREAD, M16>;
+  using G = V3W<CW, TWW>;
+  constexpr size_t lds = G::LDS;
+  auto kern = conv3x3_v3_kernel<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, SPREAD, M16, CW, TWW>;
+  const long ntiles = (long)g.B * ((g.W + G::TWV - 1) / G::TWV) * ((g.H + G::TH - 1) / G::TH);
+  if (ntiles == 0) return 0;
+  // 32-bit element offsets and tile indices inside the kernel (checked before any HIP call)
+  if ((long)g.B * g.H * g.W * CW >= (1L << 31)) return -2;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  const long ntiles = (long)g.B * ((g.W + 31) / 32) * ((g.H + 15) / 16);
-  if (ntiles == 0) return 0;
-  if ((long)g.B * g.H * g.W * 96 >= (1L << 31)) return -2;
   const int grid = (int)(ntiles < num_cus() ? ntiles : num_cus());
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, X, Wt, bias, S, Y, Y2, g, (int)ntiles,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * G::NW), lds, st, X, Wt, bias, S, Y, Y2, g, (int)ntiles,
                      g_conv_dyn ? tile_queue(st) : nullptr);
   return MSU_CHECK_LAUNCH();
 }
@@ -1483,6 +1791,24 @@ int launch_v3(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float*
   return launch_v3s<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, true, false>(g, X, Wt, bias, S, Y, Y2, st);
 }
 
+// C = 128 (Swin-B decoder head): 8-row tiles, every launch on 16x16x32 MFMA -- with one row per
+// wave only that shape lets a weight fragment feed two MFMAs, and the dgrad's accumulators (64)
+// and GELU' operands (32 registers) are fewer than at 96, so it does not spill there.
+template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL>
+int launch_v3_128(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S,
+                  bf16_t* Y, bf16_t* Y2, hipStream_t st) {
+  // (ablation 8192: the 16-row x 16-pixel geometry, two rows per wave)
+  return launch_v3s<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, true, true, 128, (MSU_EXP & 8192) ? 16 : 32>(g, X, Wt, bias, S, Y,
+                                                                                                     Y2, st);
+}
+
+// Which (dtype, Cin, Cout) take a persistent LDS-DMA kernel (msu_conv3x3_route): bit 0 the
+// forward / backward-data launches, bit 1 the weight gradient.
+inline int conv_route(bool is16, int Cin, int Cout) {
+  if (!is16 || Cin != Cout) return 0;
+  return Cin == 96 || Cin == 128 ? 3 : 0;
+}
+
 template <typename T, bool IN_D2S, bool IN_GELU, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL = false>
 int conv_nt(const ConvGeom& g, const void* X, const void* Wt, const float* bias, const void* S,
             void* Y, void* Y2, hipStream_t st) {
@@ -1491,6 +1817,9 @@ int conv_nt(const ConvGeom& g, const void* X, const void* Wt, const float* bias,
     if (g.Cout == 96 && g.CinP == 96 && g.Cin == 96)
       return launch_v3<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(g, (const bf16_t*)x, (const bf16_t*)w, bias,
                                                                   (const bf16_t*)s, (bf16_t*)y, (bf16_t*)y2, st);
+    if (g.Cout == 128 && g.CinP == 128 && g.Cin == 128 && !g_conv_generic_wide)
+      return launch_v3_128<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(g, (const bf16_t*)x, (const bf16_t*)w, bias,
+                                                                      (const bf16_t*)s, (bf16_t*)y, (bf16_t*)y2, st);
   }
   if constexpr (sizeof(T) == 2) {
     // the Swin-T/S decoder head width takes the persistent v2 kernel
@@ -1547,6 +1876,28 @@ int launch_wgrad_v2(const ConvGeom& g, const bf16_t* X, const bf16_t* DY, float*
   // every block writes its partial slabs, even with no tile (zeros)
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(768), lds, st, X, DY, part, dbpart, g, (int)ntiles);
   return MSU_CHECK_LAUNCH();
+}
+
+// C = 128: blocks 2 s + h = (pixel share s, co half h); nchunk / 2 shares, so the grid stays
+// nchunk workgroups.  Returns the number of partial chunks written (> 0) or an error (< 0).
+template <typename T, bool IN_D2S, bool IN_GELU>
+int launch_wgrad_v2h(const ConvGeom& g, const bf16_t* X, const bf16_t* DY, float* part, float* dbpart,
+                     int nchunk, hipStream_t st) {
+  constexpr int nslot = 6 * 34 * 17 + 4 * 32 * 9, nins = (nslot + 63) / 64;
+  constexpr size_t lds = 2 * sizeof(bf16_t) * (size_t)nins * 64 * 8;
+  static_assert(lds <= 160 * 1024, "LDS");
+  if ((long)g.B * g.H * g.W * 128 >= (1L << 31)) return -2;
+  auto kern = conv3x3_wgrad_v2h_kernel<T, IN_D2S, IN_GELU>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  const int nshare = nchunk >= 2 ? nchunk / 2 : 1;
+  const long ntiles = (long)g.B * ((g.W + 31) / 32) * ((g.H + 3) / 4);
+  // every block writes its partial rows, even with no tile (zeros)
+  hipLaunchKernelGGL(kern, dim3((unsigned)(2 * nshare)), dim3(768), lds, st, X, DY, part, dbpart, g, (int)ntiles);
+  return MSU_CHECK_LAUNCH() ? -1 : nshare;
 }
 
 template <typename T, bool IN_D2S, bool IN_GELU>

@@ -1,6 +1,8 @@
 // Refine-conv forward and backward-data entry points (kernels: conv3x3.h).
 #include "conv3x3.h"
 
+int conv3x3_generic_wide() { return g_conv_generic_wide; }
+
 extern "C" {
 
 // in_mode bit 0: GELU on the loaded input, bit 1: input is the pre-d2s [B,H/4,W/4,16*Cin]
@@ -72,11 +74,22 @@ int msu_conv3x3_dgrad(int dtype, int out_mode, const void* dY, const void* Wflip
   return -3;
 }
 
-// bit 0: the refine-conv kernel's tile queue (g_conv_dyn); returns the previous mode
+// bit 0: the refine-conv kernel's tile queue (g_conv_dyn); bit 1: widths other than 96 take the
+// generic kernels (the A/B handle for the C = 128 kernel).  Returns the previous mode.
 int msu_conv_mode(int mode) {
-  const int prev = g_conv_dyn;
+  const int prev = (g_conv_dyn ? 1 : 0) | (g_conv_generic_wide ? 2 : 0);
   g_conv_dyn = mode & 1;
+  g_conv_generic_wide = (mode >> 1) & 1;
   return prev;
+}
+
+// Which kernels serve a (dtype, Cin, Cout) refine conv: bit 0 forward / backward-data on a
+// persistent LDS-DMA kernel, bit 1 the weight gradient on one.  0: the generic kernels (or an
+// unsupported width).  Independent of msu_conv_mode.
+int msu_conv3x3_route(int dtype, int Cin, int Cout) {
+  if (dtype != MSU_F32 && !msu_is16(dtype)) return -2;
+  if (Cin <= 0 || Cout <= 0) return -2;
+  return conv_route(msu_is16(dtype), Cin, Cout);
 }
 
 }  // extern "C"

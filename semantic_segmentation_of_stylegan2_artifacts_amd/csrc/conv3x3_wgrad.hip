@@ -21,6 +21,7 @@ int msu_conv3x3_wgrad2(int dtype, int in_mode, const void* X, const void* dY, fl
   float* part = workspace;
   float* dbpart = workspace + (long)nchunk * 3 * Cout * 3 * g.CinP;
   int rc = -3;
+  int nsum = nchunk;  // partial chunks to sum
 #define MSU_WG(T, D2S, GL) rc = wgrad_nt<T, D2S, GL>(g, X, dY, part, dbpart, nchunk, st)
   if (msu_is16(dtype) && Cin == 96 && Cout == 96) {
     const bf16_t* x = (const bf16_t*)X; const bf16_t* d = (const bf16_t*)dY;
@@ -31,6 +32,17 @@ int msu_conv3x3_wgrad2(int dtype, int in_mode, const void* X, const void* dY, fl
         case 2: rc = launch_wgrad_v2<T, true, false>(g, x, d, part, dbpart, nchunk, st); break;
         case 3: rc = launch_wgrad_v2<T, true, true>(g, x, d, part, dbpart, nchunk, st); break;
       });
+  } else if (msu_is16(dtype) && Cin == 128 && Cout == 128 && !conv3x3_generic_wide()) {
+    // one co half per workgroup: nchunk / 2 pixel shares (conv3x3_wgrad_v2h_kernel)
+    const bf16_t* x = (const bf16_t*)X; const bf16_t* d = (const bf16_t*)dY;
+    MSU_DISPATCH16(dtype, T,
+      switch (in_mode & 3) {
+        case 0: rc = launch_wgrad_v2h<T, false, false>(g, x, d, part, dbpart, nchunk, st); break;
+        case 1: rc = launch_wgrad_v2h<T, false, true>(g, x, d, part, dbpart, nchunk, st); break;
+        case 2: rc = launch_wgrad_v2h<T, true, false>(g, x, d, part, dbpart, nchunk, st); break;
+        case 3: rc = launch_wgrad_v2h<T, true, true>(g, x, d, part, dbpart, nchunk, st); break;
+      });
+    if (rc > 0) { nsum = rc; rc = 0; }
   } else if (msu_is16(dtype)) {
     MSU_DISPATCH16(dtype, T,
       switch (in_mode & 3) {
@@ -55,7 +67,7 @@ int msu_conv3x3_wgrad2(int dtype, int in_mode, const void* X, const void* dY, fl
   float* sum = dbpart + (long)nchunk * Cout;
   const ColSeg segs[2] = {{part, slab, slab, sum}, {dbpart, Cout, Cout, db}};
   // (the slab sum is workspace, always overwritten; db and the permuted dW accumulate)
-  colsum_multi(segs, db ? 2 : 1, nchunk, 0, st, accumulate ? 2 : 0);
+  colsum_multi(segs, db ? 2 : 1, nsum, 0, st, accumulate ? 2 : 0);
   const long n = (long)Cout * Cin * 9;
   hipLaunchKernelGGL(wgrad_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sum, Cout, Cin,
                      g.CinP, dW, accumulate);

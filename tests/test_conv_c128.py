@@ -1,0 +1,170 @@
+"""CPU: the persistent refine-conv kernel at C = 128 (Swin-B decoder head, csrc/conv3x3.h):
+msu_conv3x3_route reports which widths take a persistent LDS-DMA kernel, the built library holds
+the C = 128 instantiation of conv3x3_v3_kernel for both 16-bit formats and every routed launch
+form, none of them uses scratch, and the entry points refuse bad arguments before any HIP call."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import pytest
+
+from semantic_segmentation_of_stylegan2_artifacts_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+READELF = "/opt/rocm/llvm/bin/llvm-readelf"
+F32, BF16, F16 = 0, 1, 2
+
+# the weight gradient at 128 ships too (conv3x3_wgrad_v2h_kernel): bit 1 is set
+WGRAD_128 = True
+
+# launch forms routed to the persistent kernel, as template flags
+# (IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL): forward plain / d2s, each with and without the dual
+# GELU output; backward-data with GELU'(S), plain and scattered through the d2s map
+FORMS = [(0, 0, 0, 1, 0), (1, 0, 0, 1, 0), (0, 0, 0, 1, 1), (1, 0, 0, 1, 1), (0, 0, 1, 0, 0), (0, 1, 1, 0, 0)]
+
+
+def _kernel_metadata(lib):
+    """{kernel symbol: {field: value}} from the code-object notes of the gfx950 code in lib."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import lds_hazard_check as chk
+    finally:
+        sys.path.pop(0)
+    work = tempfile.mkdtemp(prefix="msu_meta_")
+    out = {}
+    try:
+        for obj in chk.extract_code_objects(lib, work):
+            notes = subprocess.run([READELF, "--notes", obj], check=True, capture_output=True, text=True).stdout
+            for block in re.split(r"\n\s*- \.", notes):
+                name = re.search(r"\.name:\s+(\S+)", block)
+                if name is None or ".vgpr_count:" not in block:
+                    continue
+                out[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*(?:\n|$)", block)}
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    return out
+
+
+def test_route_reports_the_persistent_widths():
+    L = _lib.lib()
+    for dt in (BF16, F16):
+        assert L.msu_conv3x3_route(dt, 96, 96) == 3
+        r = L.msu_conv3x3_route(dt, 128, 128)
+        assert r & 1, "forward / backward-data at 128 take the persistent kernel"
+        assert bool(r & 2) == WGRAD_128 and r in (1, 3)
+        for cin, cout in ((128, 96), (96, 128), (64, 64), (32, 32), (112, 112)):
+            assert L.msu_conv3x3_route(dt, cin, cout) == 0, (cin, cout)
+    for c in (96, 128, 64):
+        assert L.msu_conv3x3_route(F32, c, c) == 0
+
+
+def test_route_does_not_depend_on_the_mode_bits():
+    L = _lib.lib()
+    prev = L.msu_conv_mode(3)
+    try:
+        assert L.msu_conv_mode(3) == 3, "both mode bits are kept and reported"
+        assert L.msu_conv3x3_route(BF16, 128, 128) & 1
+        L.msu_conv_mode(2)
+        assert L.msu_conv_mode(1) == 2
+        assert L.msu_conv_mode(1) == 1
+    finally:
+        L.msu_conv_mode(prev)
+    assert prev in (0, 1), "bit 1 is off unless a tool or test sets it"
+
+
+def test_argument_checks_come_before_any_hip_call():
+    """-2 for every refused call; the pointers are never touched (all but the bias are null)."""
+    L = _lib.lib()
+    assert L.msu_conv3x3_route(7, 128, 128) == -2
+    assert L.msu_conv3x3_route(BF16, 0, 128) == -2
+    assert L.msu_conv3x3_route(BF16, 128, -128) == -2
+    bias = (ctypes.c_float * 128)()
+    pb = ctypes.cast(bias, ctypes.c_void_p)
+    for dt in (BF16, F16):
+        # d2s needs H, W % 4 == 0; a dual output excludes GELU on load; no bias
+        assert L.msu_conv3x3_fwd2(dt, 2, None, None, pb, None, None, 1, 18, 16, 128, 128, None) == -2
+        assert L.msu_conv3x3_fwd2(dt, 1, None, None, pb, None, pb, 1, 16, 16, 128, 128, None) == -2
+        assert L.msu_conv3x3_fwd2(dt, 0, None, None, None, None, None, 1, 16, 16, 128, 128, None) == -2
+        assert L.msu_conv3x3_dgrad(dt, 3, None, None, None, None, 1, 16, 18, 128, 128, None) == -2
+        # 2^31 elements: past the kernel's 32-bit offsets
+        assert L.msu_conv3x3_fwd2(dt, 0, None, None, pb, None, None, 1, 4096, 4096, 128, 128, None) == -2
+        assert L.msu_conv3x3_dgrad(dt, 1, None, None, None, None, 1, 4096, 4096, 128, 128, None) == -2
+        # widths the refine convs do not have
+        assert L.msu_conv3x3_fwd2(dt, 0, None, None, pb, None, None, 1, 16, 16, 128, 136, None) == -2
+        assert L.msu_conv3x3_dgrad(dt, 1, None, None, None, None, 1, 16, 16, 132, 128, None) == -2
+
+
+@pytest.fixture(scope="module")
+def v3_meta():
+    assert os.path.exists(READELF), READELF
+    return {k: v for k, v in _kernel_metadata(_lib.LIB_PATH).items() if "conv3x3_v3_kernel" in k}
+
+
+def _symbol(fmt, form, C):
+    # 16x16x32 MFMA form with the halo loads spread over the taps, then width and tile width:
+    # conv3x3_v3_kernel<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, SPREAD = true, M16 = true, C, 32>
+    flags = "".join(f"Lb{b}E" for b in form) + "Lb1ELb1E"
+    return f"conv3x3_v3_kernelI{fmt}{flags}Li{C}ELi32EEE"
+
+
+@pytest.mark.parametrize("fmt", ["t", "DF16_"], ids=["bf16", "f16"])
+@pytest.mark.parametrize("form", FORMS, ids=["fwd", "fwd_d2s", "fwd_dual", "fwd_d2s_dual", "dgrad", "dgrad_d2s"])
+def test_c128_instantiations_present_and_without_scratch(v3_meta, fmt, form):
+    hits = [k for k in v3_meta if _symbol(fmt, form, 128) in k]
+    assert len(hits) == 1, (_symbol(fmt, form, 128), sorted(v3_meta))
+    m = v3_meta[hits[0]]
+    # every field indexed directly: a renamed key is an error, not a pass
+    assert m["private_segment_fixed_size"] == 0, m
+    assert m["vgpr_spill_count"] == 0, m
+    assert m["sgpr_spill_count"] == 0, m
+    assert m["vgpr_count"] <= 256, m
+    assert m["group_segment_fixed_size"] <= 160 * 1024, m
+    assert m["max_flat_workgroup_size"] == 512, m
+
+
+def test_only_the_two_widths_are_built(v3_meta):
+    widths = {int(re.search(r"Li(\d+)ELi32EEE", k).group(1)) for k in v3_meta}
+    assert widths == {96, 128}, widths
+    assert len([k for k in v3_meta if "Li128ELi" in k]) == 2 * len(FORMS), "no 32x32x16 form, one geometry at 128"
+    # the C = 96 forms launched today are all still there (16x16x32 forward, 32x32x16 dgrad)
+    for fmt in ("t", "DF16_"):
+        for form in FORMS:
+            m16 = 0 if form[2] else 1
+            flags = "".join(f"Lb{b}E" for b in form) + f"Lb1ELb{m16}E"
+            assert any(f"conv3x3_v3_kernelI{fmt}{flags}Li96ELi32EEE" in k for k in v3_meta), (fmt, form)
+
+
+@pytest.mark.parametrize("fmt", ["t", "DF16_"], ids=["bf16", "f16"])
+@pytest.mark.parametrize("d2s,gelu", [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_c128_wgrad_instantiations_without_scratch(fmt, d2s, gelu):
+    meta = {k: v for k, v in _kernel_metadata(_lib.LIB_PATH).items() if "conv3x3_wgrad_v2h_kernel" in k}
+    assert len(meta) == 8, sorted(meta)
+    hits = [k for k in meta if f"conv3x3_wgrad_v2h_kernelI{fmt}Lb{d2s}ELb{gelu}EEE" in k]
+    assert len(hits) == 1, sorted(meta)
+    m = meta[hits[0]]
+    assert m["private_segment_fixed_size"] == 0, m
+    assert m["vgpr_spill_count"] == 0, m
+    assert m["sgpr_spill_count"] == 0, m
+    assert m["vgpr_count"] <= 168, m   # 12 waves per workgroup: three per SIMD
+    assert m["max_flat_workgroup_size"] == 768, m
+
+
+def test_wgrad_argument_checks_come_before_any_hip_call():
+    L = _lib.lib()
+    for dt in (BF16, F16):
+        # 2^31 elements; no chunks
+        assert L.msu_conv3x3_wgrad2(dt, 0, None, None, None, None, None, 4, 1, 4096, 4096, 128, 128, 0, None) == -2
+        assert L.msu_conv3x3_wgrad2(dt, 0, None, None, None, None, None, 0, 1, 16, 16, 128, 128, 0, None) == -2
+    assert L.msu_conv3x3_wgrad_workspace(256, 128, 128, 0, 0) == 257 * 3 * 128 * 3 * 128 + 256 * 128
+
+
+def test_dynamic_lds_of_both_widths_fits():
+    """The kernel's LDS is dynamic (halo + two weight images + bias + queue entry); the sizes
+    the launcher asks for, recomputed from the tile geometry."""
+    for C, rows in ((96, 16), (128, 8)):
+        lds = 2 * ((rows + 2) * 34 * C + 2 * C * C) + 4 * C + 16
+        assert lds <= 160 * 1024, (C, lds)

@@ -11,7 +11,7 @@ import sys
 
 def main():
     trace, bench = sys.argv[1], sys.argv[2]
-    sub = sys.argv[3] if len(sys.argv) > 3 else "conv3x3_v3_kernel<unsigned short, false, false, false, true, false, true, true>"
+    sub = sys.argv[3] if len(sys.argv) > 3 else "conv3x3_v3_kernel<unsigned short, false, false, false, true, false, true, true, 96, 32>"
     rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
     best, run = [], []
     for r in rows:
