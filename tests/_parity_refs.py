@@ -7,6 +7,10 @@
 * ``decode_keep_bits``: the 16-bit attention forward's stored keep bits
   (csrc/window_attention_mfma.hip, ``[window x head][query tile][lane]`` words; bit jt*16 + r of
   lane l in tile it <-> query 32 it + (l & 31), key 32 jt + crow(r, l >> 5)) -> [items, 49, 49].
+  What those bits should be is restated on the host in ``tests/_attn_mask_ref.py``
+  (``keep_mask``: the dropout streams of csrc/common.h in numpy, same [items, 49, 49] layout);
+  tests/test_gpu_attn_dropout.py compares the two and evaluates ``attn_ref_from_qkv`` in float64
+  with the host mask.
 * ``conv3x3_ref``: ``conv2d(a, W, b, padding=1)`` on NHWC tensors as nine shifted fp32
   matmuls (autograd gives dA, dW, db), so the 1024^2 references need neither the CPU nor a
   library convolution.
