@@ -180,10 +180,13 @@ int msu_conv3x3_wgrad2(int dtype, int in_mode, const void* X, const void* dY, fl
                        void* stream);
 
 /* ---------------------------------------------------------------- fused qkv Linear + window attention
- * Stage 0 of the Swin block (C = 96, 3 heads; model_parts.py:166-170 -> torchvision's qkv Linear and
+ * Stage 0 of the Swin block (model_parts.py:166-170 -> torchvision's qkv Linear and
  * shifted_window_attention in one kernel): out[B,H,W,C] = attention(x W_qkv^T + b_qkv), x the LN1
  * rows (16-bit), W_qkv [3C][C] 16-bit, b_qkv f32.  qkv_out (nullable) receives x W^T + b (the qkv
- * Linear's output, for the backward); dropout / keep bits / aux workspace as msu_win_attn_fwd. */
+ * Linear's output, for the backward); dropout / keep bits / aux workspace as msu_win_attn_fwd.
+ * Built for the two stage-0 widths: (C, nh) = (96, 3) (Swin-T/S) and (128, 4) (Swin-B), bf16 / f16;
+ * msu_win_attn_qkv_supported says which, and the forwards return -2 before any launch for
+ * every other (C, nh), for f32, and for B H W 3C >= 2^32 (32-bit row offsets). */
 int msu_win_attn_qkv_supported(int C, int nh);
 int msu_win_attn_qkv_fwd(int dtype, const void* x, const void* w_qkv, const float* b_qkv, const float* table,
                          void* out, void* qkv_out, void* keep, float* workspace, int B, int H, int W, int C, int nh,
@@ -191,7 +194,8 @@ int msu_win_attn_qkv_fwd(int dtype, const void* x, const void* w_qkv, const floa
                          void* stream);
 /* The whole attention half of the block: out = (attention(x W_qkv^T + b_qkv)) W_proj^T + b_proj
  * (model_parts.py:166-170 with the proj Linear); o_out (nullable) receives the attention output
- * before proj (the proj weight gradient's input), qkv_out as above. */
+ * before proj (the proj weight gradient's input), qkv_out as above.  At both widths qkv and o are
+ * written only when their pointers are given (a no-grad call writes neither). */
 int msu_win_attn_qkv_fwd2(int dtype, const void* x, const void* w_qkv, const float* b_qkv, const float* table,
                           const void* w_proj, const float* b_proj, void* out, void* o_out, void* qkv_out, void* keep,
                           float* workspace, int B, int H, int W, int C, int nh, int shift, float p_drop,

@@ -1012,35 +1012,129 @@ int msu_attn_mfma_bwd_tail(float* ws, float* dtable, float* dqkv_bias_pad, long 
 //     fragment reads);
 //   * attention as attn_fwd_mfma (transposed scores, bias image from the aux workspace, the
 //     same dropout streams and keep-bit layout, so the existing backward consumes it).
-// Stage-0 widths only (C = 96, 3 heads).
+// Stage-0 widths: C = 96 with 3 heads (Swin-T/S) as above, and C = 128 with 4 heads (Swin-B), where
+// that layout is 211 KB and does not fit a CU's 160 KiB.  At 128 (8 waves, 158,208 B):
+//   * W_qkv [384][128] resident (96 KB), the LN1 rows [64][128] register-staged as above, only
+//     the k and v images of the four heads in LDS (40 KB);
+//   * a wave's q never leaves its registers: its 32 queries are the accumulator of its own qkv
+//     GEMM, and after bias and rounding a permlane32 swap (store_slice's pairing) puts them in
+//     the B-operand order of S^T = K Q^T;
+//   * o goes through the LN1 rows' buffer (free after the qkv GEMM), where the proj GEMM reads
+//     it as a swizzled [64][128] image; y is staged in the k / v space (free after the attention);
+//   * W_proj is not in LDS: wave (h, t) multiplies by rows 32h .. 32h + 31 only, the same 8
+//     A-operand fragments for every window, read once from global memory into 32 registers;
+//   * rows of W / x / y use the 16-B chunk swizzle c ^ (r & 15): 256-B rows all start on bank 0,
+//     so (r >> 2) & 3 leaves 4 rows on every bank column.
 namespace {
 
-constexpr int FQ_C = 96, FQ_NH = 3, FQ_C3 = 3 * FQ_C, FQ_CH = FQ_C / 8;  // 12 16-B chunks per row
-constexpr int FQ_WAVES = 2 * FQ_NH;
+template <int CW>
+struct FQ {
+  static_assert(CW == 96 || CW == 128, "fused unit: stage-0 widths only");
+  static constexpr int C = CW, NH = CW / HD, C3 = 3 * CW, CH = CW / 8;  // CH 16-B chunks per row
+  static constexpr int WAVES = 2 * NH, NTHR = 64 * WAVES;
+  static constexpr bool WIDE = CW == 128;
+};
 
-struct FusedLds {
-  bf16_t w[FQ_C3 * FQ_C];        // W_qkv rows (swizzled chunks)
-  bf16_t wp[FQ_C * FQ_C];        // W_proj rows (swizzled chunks; PROJ)
-  bf16_t x[64 * FQ_C];           // the window's LN1 rows (swizzled chunks); PROJ: then its output rows
-  bf16_t qkv[FQ_NH][3][64 * LD];  // per head: q, k, v images [t][d] (padded rows); q then o
-  float bias[FQ_C3];
-  float pbias[FQ_C];
+template <int CW>
+struct FusedLds {  // C = 96
+  bf16_t w[FQ<CW>::C3 * CW];          // W_qkv rows (swizzled chunks)
+  bf16_t wp[CW * CW];                 // W_proj rows (swizzled chunks; PROJ)
+  bf16_t x[64 * CW];                  // the window's LN1 rows (swizzled chunks); PROJ: then its output rows
+  bf16_t qkv[FQ<CW>::NH][3][64 * LD];  // per head: q, k, v images [t][d] (padded rows); q then o
+  float bias[FQ<CW>::C3];
+  float pbias[CW];
   int tok[64], reg[64];
 };
 
-MSU_DEV int fq_swz(int r) { return (r >> 2) & 3; }
+template <>
+struct FusedLds<128> {
+  bf16_t w[384 * 128];       // W_qkv rows (swizzled chunks)
+  bf16_t x[64 * 128];        // the window's LN1 rows (swizzled chunks); then o of all heads
+  bf16_t kv[4][2][64 * LD];  // per head: k, v images [t][d] (padded rows); PROJ: then the output rows
+  float bias[384];
+  float pbias[128];
+  int tok[64], reg[64];
+};
+static_assert(sizeof(FusedLds<96>) == 134144, "fused unit: the C = 96 layout is the round-4 one");
+static_assert(sizeof(FusedLds<128>) == 158208 && sizeof(FusedLds<128>) <= 160 * 1024, "fused unit: LDS budget at 128");
+static_assert(sizeof(FusedLds<128>::kv) >= sizeof(FusedLds<128>::x), "the output rows are staged in the k / v space");
 
-// 32-row k-contiguous fragment of a swizzled [rows][96] image: lane -> row r0 + (lane & 31),
-// k = 16 ks + 8 (lane >> 5) .. + 7
-MSU_DEV bf16x8 fq_frag(const bf16_t* img, int r0, int ks, int lane) {
-  const int r = r0 + (lane & 31);
-  return *reinterpret_cast<const bf16x8*>(img + r * FQ_C + (((2 * ks + (lane >> 5)) ^ fq_swz(r)) << 3));
+template <int CW>
+MSU_DEV constexpr int fq_swz(int r) {
+  return CW == 128 ? (r & 15) : ((r >> 2) & 3);
 }
 
-// PROJ: the proj Linear too -- y = o W_proj^T + b_proj from the three heads' o (in LDS) is the
+// ds_read_b128 serves lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32) together, each group
+// over all 64 banks: conflict-free when a group's 16 lanes hit 16 distinct 16-B bank columns
+constexpr int fq_b128_lane(int g, int i) {
+  const int l = (g & 1) == 0 ? (i < 4 ? i : i < 8 ? i + 8 : i + 12) : (i < 8 ? i + 4 : i < 12 ? i + 8 : i + 16);
+  return l + 32 * (g >> 1);
+}
+// every fq_frag read of a swizzled [rows][CW] image (first row a multiple of 32, any k step)
+template <int CW>
+constexpr bool fq_frag_reads_conflict_free() {
+  for (int r0 = 0; r0 + 32 <= FQ<CW>::C3; r0 += 32)
+    for (int ks = 0; ks < CW / 16; ++ks)
+      for (int g = 0; g < 4; ++g) {
+        unsigned cols = 0;
+        for (int i = 0; i < 16; ++i) {
+          const int lane = fq_b128_lane(g, i), r = r0 + (lane & 31);
+          cols |= 1u << ((r * FQ<CW>::CH + ((2 * ks + (lane >> 5)) ^ fq_swz<CW>(r))) & 15);
+        }
+        if (cols != 0xffffu) return false;
+      }
+  return true;
+}
+// the 16-B staging writes (slot s = row s / CH, chunk s % CH; ds_write_b128 serves 8 consecutive
+// lanes over 32 banks: 8 distinct 16-B columns mod 8)
+template <int CW>
+constexpr bool fq_stage_writes_conflict_free() {
+  for (int s0 = 0; s0 < 64 * FQ<CW>::CH; s0 += 8) {
+    unsigned cols = 0;
+    for (int s = s0; s < s0 + 8; ++s) {
+      const int r = s / FQ<CW>::CH, c = s % FQ<CW>::CH;
+      cols |= 1u << ((r * FQ<CW>::CH + (c ^ fq_swz<CW>(r))) & 7);
+    }
+    if (cols != 0xffu) return false;
+  }
+  return true;
+}
+static_assert(fq_frag_reads_conflict_free<96>() && fq_frag_reads_conflict_free<128>(), "W / x image: bank conflicts");
+static_assert(fq_stage_writes_conflict_free<96>() && fq_stage_writes_conflict_free<128>(), "row staging: bank conflicts");
+
+// 32-row k-contiguous fragment of a swizzled [rows][CW] image: lane -> row r0 + (lane & 31),
+// k = 16 ks + 8 (lane >> 5) .. + 7
+template <int CW>
+MSU_DEV bf16x8 fq_frag(const bf16_t* img, int r0, int ks, int lane) {
+  const int r = r0 + (lane & 31);
+  return *reinterpret_cast<const bf16x8*>(img + r * CW + (((2 * ks + (lane >> 5)) ^ fq_swz<CW>(r)) << 3));
+}
+
+// q of a lane-major accumulator (lane = token, registers 4g .. 4g+3 = d 8g + 4hh .. + 3) + bias,
+// rounded to 16 bits, as the B operand of S^T = K Q^T: qf[ks] of lane half hh = d 16 ks + 8 hh .. + 7
+// (the permlane32 pairing of store_slice).  Every lane must execute it.
+template <typename T>
+MSU_DEV void fq_q_operand(const f32x16& a, const float* bias, int hh, bf16x8 (&qf)[2]) {
+  uint32_t w[8];
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq) {
+    const float4 b = *reinterpret_cast<const float4*>(bias + 8 * gq + 4 * hh);
+    w[2 * gq] = pack2<T>(a[4 * gq] + b.x, a[4 * gq + 1] + b.y);
+    w[2 * gq + 1] = pack2<T>(a[4 * gq + 2] + b.z, a[4 * gq + 3] + b.w);
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const auto s0 = __builtin_amdgcn_permlane32_swap(w[4 * p], w[4 * p + 2], false, false);
+    const auto s1 = __builtin_amdgcn_permlane32_swap(w[4 * p + 1], w[4 * p + 3], false, false);
+    const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};
+    qf[p] = __builtin_bit_cast(bf16x8, v);
+  }
+}
+
+// PROJ: the proj Linear too -- y = o W_proj^T + b_proj from the heads' o (in LDS) is the
 // output (`out`), and o itself goes to o_out (the proj weight gradient's input) when given.
-template <typename T, bool DROP, bool STORE_QKV, bool PROJ>
-__global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t* __restrict__ xin,
+template <typename T, int CW, bool DROP, bool STORE_QKV, bool PROJ>
+__global__ void __launch_bounds__(FQ<CW>::NTHR) attn_qkv_fwd_mfma(const bf16_t* __restrict__ xin,
                                                                   const bf16_t* __restrict__ wqkv,
                                                                   const float* __restrict__ bqkv, Aux aux,
                                                                   bf16_t* __restrict__ out, bf16_t* __restrict__ qkv_out,
@@ -1051,28 +1145,41 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
                                                                   const float* __restrict__ bproj,
                                                                   bf16_t* __restrict__ o_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  FusedLds& L = *reinterpret_cast<FusedLds*>(smem_raw);
+  FusedLds<CW>& L = *reinterpret_cast<FusedLds<CW>*>(smem_raw);
+  constexpr int FQ_C = CW, FQ_C3 = FQ<CW>::C3, FQ_CH = FQ<CW>::CH, NTHR = FQ<CW>::NTHR;
+  constexpr bool WIDE = FQ<CW>::WIDE;
   const uint64_t seed = launch_seed(seed0, seed_dev);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = wave >> 1, t = wave & 1, hh = lane >> 5;
-  constexpr int NTHR = 64 * FQ_WAVES;
   // resident W_qkv and bias
   for (int s = tid; s < FQ_C3 * FQ_CH; s += NTHR) {
     const int r = s / FQ_CH, c = s - (s / FQ_CH) * FQ_CH;
-    *reinterpret_cast<u32x4*>(L.w + r * FQ_C + ((c ^ fq_swz(r)) << 3)) =
+    *reinterpret_cast<u32x4*>(L.w + r * FQ_C + ((c ^ fq_swz<CW>(r)) << 3)) =
         *reinterpret_cast<const u32x4*>(wqkv + r * FQ_C + 8 * c);
   }
   for (int s = tid; s < FQ_C3; s += NTHR) L.bias[s] = bqkv[s];
+  // WIDE: this wave's W_proj rows 32h .. 32h + 31 as A-operand fragments (fq_frag's lane mapping
+  // on the plain row-major weight), the same for every window
+  bf16x8 wpf[WIDE && PROJ ? FQ_C / 16 : 1];
+  auto load_wproj = [&](const bf16_t* wp) __attribute__((always_inline)) {
+#pragma unroll
+    for (int ks = 0; ks < FQ_C / 16; ++ks)
+      wpf[ks] = *reinterpret_cast<const bf16x8*>(wp + (32 * h + (lane & 31)) * FQ_C + 16 * ks + 8 * hh);
+  };
   if constexpr (PROJ) {
-    for (int s = tid; s < FQ_C * FQ_CH; s += NTHR) {
-      const int r = s / FQ_CH, c = s - (s / FQ_CH) * FQ_CH;
-      *reinterpret_cast<u32x4*>(L.wp + r * FQ_C + ((c ^ fq_swz(r)) << 3)) =
-          *reinterpret_cast<const u32x4*>(wproj + r * FQ_C + 8 * c);
+    if constexpr (WIDE) {
+      load_wproj(wproj);
+    } else {
+      for (int s = tid; s < FQ_C * FQ_CH; s += NTHR) {
+        const int r = s / FQ_CH, c = s - (s / FQ_CH) * FQ_CH;
+        *reinterpret_cast<u32x4*>(L.wp + r * FQ_C + ((c ^ fq_swz<CW>(r)) << 3)) =
+            *reinterpret_cast<const u32x4*>(wproj + r * FQ_C + 8 * c);
+      }
     }
     for (int s = tid; s < FQ_C; s += NTHR) L.pbias[s] = bproj[s];
   }
-  // the window's 64 x 12 chunks of LN1 rows: thread -> slots tid, tid + NTHR
+  // the window's 64 x CH chunks of LN1 rows: thread -> slots tid, tid + NTHR
   constexpr int XS = (64 * FQ_CH + NTHR - 1) / NTHR;  // 2
   u32x4 xr[XS];
   int tokr = TOK_ZERO, regr = 0;  // thread tid < 64: token-table entry tid of the staged window
@@ -1100,7 +1207,7 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
     for (int k = 0; k < XS; ++k) {
       const int s = tid + NTHR * k;
       const int r = s / FQ_CH, c = s - (s / FQ_CH) * FQ_CH;
-      if (s < 64 * FQ_CH) *reinterpret_cast<u32x4*>(L.x + r * FQ_C + ((c ^ fq_swz(r)) << 3)) = xr[k];
+      if (s < 64 * FQ_CH) *reinterpret_cast<u32x4*>(L.x + r * FQ_C + ((c ^ fq_swz<CW>(r)) << 3)) = xr[k];
     }
     if (tid < 64) {
       L.tok[tid] = tokr;
@@ -1128,16 +1235,24 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
     for (int m = 0; m < 3; ++m) acc[m] = f32x16{0};
 #pragma unroll
     for (int ks = 0; ks < FQ_C / 16; ++ks) {
-      const bf16x8 xf = fq_frag(L.x, 32 * t, ks, lane);
+      // WIDE: the 32 fragment reads of the 8 k steps, all hoisted, are 128 registers beside the
+      // accumulators, the bias image and the W_proj fragments (one instantiation spilled): two halves
+      if constexpr (WIDE)
+        if (ks == FQ_C / 32) __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 xf = fq_frag<CW>(L.x, 32 * t, ks, lane);
 #pragma unroll
-      for (int m = 0; m < 3; ++m) acc[m] = mfma32<T>(fq_frag(L.w, m * FQ_C + 32 * h, ks, lane), xf, acc[m]);
+      for (int m = 0; m < 3; ++m) acc[m] = mfma32<T>(fq_frag<CW>(L.w, m * FQ_C + 32 * h, ks, lane), xf, acc[m]);
     }
     // + bias, round to 16 bits, rows of the q / k / v images (lane = token, registers 4g .. 4g+3 =
-    // channels 8g + 4hh .. + 3)
+    // channels 8g + 4hh .. + 3); WIDE: q stays in registers as the scores' B operand
     const int tk = 32 * t + (lane & 31);
+    bf16x8 qreg[2];
+    if constexpr (WIDE) fq_q_operand<T>(acc[0], L.bias + 32 * h, hh, qreg);
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      bf16_t* img = L.qkv[h][m];
+    for (int m = WIDE ? 1 : 0; m < 3; ++m) {
+      bf16_t* img;
+      if constexpr (WIDE) img = L.kv[h][m - 1];
+      else img = L.qkv[h][m];
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const float4 b = *reinterpret_cast<const float4*>(L.bias + m * FQ_C + 32 * h + 8 * gq + 4 * hh);
@@ -1151,29 +1266,54 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
     if constexpr (STORE_QKV) {
       // the training path keeps qkv for the backward: this wave's tokens, head h's three
       // 64-B slices, 4 lanes per slice (16 whole slices per store instruction)
+      if constexpr (WIDE) {
+        // q from the registers: the lane's token, d 16 p + 8 hh .. + 7 (two 16-B pieces)
+        const int tok = L.tok[tk];
 #pragma unroll
-      for (int m = 0; m < 3; ++m)
+        for (int p = 0; p < 2; ++p)
+          if (tok >= 0)
+            *reinterpret_cast<bf16x8*>(qkv_out + (size_t)((unsigned)tok * (unsigned)FQ_C3) + h * HD + 16 * p + 8 * hh) =
+                qreg[p];
+      }
+#pragma unroll
+      for (int m = WIDE ? 1 : 0; m < 3; ++m)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int r = 32 * t + read_row(lane >> 2) + 16 * c;
           const int tok = L.tok[r];
-          const u32x4 v = *reinterpret_cast<const u32x4*>(L.qkv[h][m] + r * LD + 8 * (lane & 3));
+          const bf16_t* img;
+          if constexpr (WIDE) img = L.kv[h][m - 1];
+          else img = L.qkv[h][m];
+          const u32x4 v = *reinterpret_cast<const u32x4*>(img + r * LD + 8 * (lane & 3));
           if (tok >= 0)
             *reinterpret_cast<u32x4*>(qkv_out + (size_t)((unsigned)tok * (unsigned)FQ_C3) + m * FQ_C + h * HD +
                                       8 * (lane & 3)) = v;
         }
     }
     // ---- attention of head h, query tile t (as attn_fwd_mfma)
-    const bf16_t* Lq = L.qkv[h][0];
-    const bf16_t* Lk = L.qkv[h][1];
-    const bf16_t* Lv = L.qkv[h][2];
+    const bf16_t *Lq = nullptr, *Lk, *Lv;
+    if constexpr (WIDE) {
+      Lk = L.kv[h][0];
+      Lv = L.kv[h][1];
+      if constexpr (PROJ && (MSU_EXP & 128) != 0) {  // timing variant: W_proj fragments from L2 every window
+        const bf16_t* wp = wproj;
+        asm volatile("" : "+s"(wp));
+        load_wproj(wp);
+      }
+    } else {
+      Lq = L.qkv[h][0];
+      Lk = L.qkv[h][1];
+      Lv = L.qkv[h][2];
+    }
     uint32_t kmask = ~0u;
     if constexpr (DROP)
       kmask = drop_bits<false>(drop_seed32(seed), (uint32_t)win * g.nh + h, t * 32 + (lane & 31), hh,
                                drop_thresh16(p_drop));
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const bf16x8 qf = frag_rows(Lq, LD, 32 * t, 16 * ks, lane);
+      bf16x8 qf;
+      if constexpr (WIDE) qf = qreg[ks];
+      else qf = frag_rows(Lq, LD, 32 * t, 16 * ks, lane);
 #pragma unroll
       for (int jt = 0; jt < 2; ++jt) P[jt] = mfma32<T>(frag_rows(Lk, LD, 32 * jt, 16 * ks, lane), qf, P[jt]);
     }
@@ -1185,15 +1325,19 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
     for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb) O = mfma32<T>(frag_tr_perm(Lv, LD, jt * 32 + 16 * sb, 0, lane), pack8<T>(P[jt], sb), O);
-    // output through this tile's q rows (read only by this wave)
-    bf16_t* Lo = L.qkv[h][0];
+    // output through this tile's q rows (read only by this wave); WIDE: through columns 32h ..
+    // 32h + 31 of this tile's LN1 rows (every wave's GEMM reads of them are behind the barrier above)
+    auto orow = [&](int r, int d) __attribute__((always_inline)) -> bf16_t* {  // d: a multiple of 4
+      if constexpr (WIDE) return L.x + r * FQ_C + (((4 * h + (d >> 3)) ^ fq_swz<CW>(r)) << 3) + (d & 7);
+      else return L.qkv[h][0] + r * LD + d;
+    };
     const int i = t * 32 + (lane & 31);
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
       uint2 wv;
       wv.x = pack2<T>(O[4 * gq], O[4 * gq + 1]);
       wv.y = pack2<T>(O[4 * gq + 2], O[4 * gq + 3]);
-      *reinterpret_cast<uint2*>(Lo + i * LD + 8 * gq + 4 * hh) = wv;
+      *reinterpret_cast<uint2*>(orow(i, 8 * gq + 4 * hh)) = wv;
     }
     lds_sync();
     bf16_t* const odst = PROJ ? o_out : out;
@@ -1202,23 +1346,31 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
       for (int c = 0; c < 2; ++c) {
         const int r = 32 * t + read_row(lane >> 2) + 16 * c;
         const int tok = L.tok[r];
-        const u32x4 v = *reinterpret_cast<const u32x4*>(Lo + r * LD + 8 * (lane & 3));
+        const u32x4 v = *reinterpret_cast<const u32x4*>(orow(r, 8 * (lane & 3)));
         if (tok >= 0)
           *reinterpret_cast<u32x4*>(odst + (size_t)((unsigned)tok * (unsigned)FQ_C) + h * HD + 8 * (lane & 3)) = v;
       }
     }
     if (DROP && keep_out) keep_out[((size_t)win * g.nh + h) * 128 + 64 * t + lane] = kmask;
     if constexpr (PROJ) {
-      __syncthreads();  // o of every head in LDS (q image rows)
+      __syncthreads();  // o of every head in LDS (q image rows; WIDE: the LN1 rows' buffer)
       // y[token][n] = sum_d o[token][d] W_proj[n][d] + b: wave -> (token tile t, n tile h); the
       // k steps of 16 d walk the heads' o images (d = 32 h' + 16 (ks & 1) + ...)
       f32x16 ya = f32x16{0};
 #pragma unroll
       for (int ks = 0; ks < FQ_C / 16; ++ks) {
-        const bf16x8 of = frag_rows(L.qkv[ks >> 1][0], LD, 32 * t, 16 * (ks & 1), lane);
-        ya = mfma32<T>(fq_frag(L.wp, 32 * h, ks, lane), of, ya);
+        if constexpr (WIDE) {
+          ya = mfma32<T>(wpf[ks], fq_frag<CW>(L.x, 32 * t, ks, lane), ya);
+        } else {
+          const bf16x8 of = frag_rows(L.qkv[ks >> 1][0], LD, 32 * t, 16 * (ks & 1), lane);
+          ya = mfma32<T>(fq_frag<CW>(L.wp, 32 * h, ks, lane), of, ya);
+        }
       }
-      // + bias, rows of the output image (the LN1 rows' buffer, free since the qkv GEMM)
+      // + bias, rows of the output image (the LN1 rows' buffer, free since the qkv GEMM; WIDE: the
+      // k / v images' space, free since the barrier above -- the LN1 rows' buffer holds o)
+      bf16_t* ybuf;
+      if constexpr (WIDE) ybuf = &L.kv[0][0][0];
+      else ybuf = L.x;
       const int tk2 = 32 * t + (lane & 31);
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
@@ -1228,7 +1380,7 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
         wv.x = pack2<T>(ya[4 * gq] + b.x, ya[4 * gq + 1] + b.y);
         wv.y = pack2<T>(ya[4 * gq + 2] + b.z, ya[4 * gq + 3] + b.w);
         // chunk n / 8 of row tk2, 8-B half 4hh / 4 of it (swizzled chunks as the LN1 rows)
-        *reinterpret_cast<uint2*>(L.x + tk2 * FQ_C + (((n >> 3) ^ fq_swz(tk2)) << 3) + 4 * hh) = wv;
+        *reinterpret_cast<uint2*>(ybuf + tk2 * FQ_C + (((n >> 3) ^ fq_swz<CW>(tk2)) << 3) + 4 * hh) = wv;
       }
       __syncthreads();
 #pragma unroll
@@ -1237,7 +1389,7 @@ __global__ void __launch_bounds__(64 * FQ_WAVES) attn_qkv_fwd_mfma(const bf16_t*
         const int r = s / FQ_CH, c = s - (s / FQ_CH) * FQ_CH;
         if (s < 64 * FQ_CH) {
           const int tok = L.tok[r];
-          const u32x4 v = *reinterpret_cast<const u32x4*>(L.x + r * FQ_C + ((c ^ fq_swz(r)) << 3));
+          const u32x4 v = *reinterpret_cast<const u32x4*>(ybuf + r * FQ_C + ((c ^ fq_swz<CW>(r)) << 3));
           if (tok >= 0) *reinterpret_cast<u32x4*>(out + (size_t)((unsigned)tok * (unsigned)FQ_C) + 8 * c) = v;
         }
       }
@@ -1256,43 +1408,57 @@ int num_cus_fq() {
   return cus;
 }
 
-template <typename T, bool DROP, bool STORE_QKV, bool PROJ>
+template <typename T, int CW, bool DROP, bool STORE_QKV, bool PROJ>
 void launch_fq(dim3 grid, const void* x, const void* w, const float* b, const Aux& aux, void* out, void* qkv, Geom g,
                float scale, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, void* keep,
                const void* wp, const float* bp, void* o_out, hipStream_t st) {
-  auto kern = attn_qkv_fwd_mfma<T, DROP, STORE_QKV, PROJ>;
+  auto kern = attn_qkv_fwd_mfma<T, CW, DROP, STORE_QKV, PROJ>;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FusedLds));
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)sizeof(FusedLds<CW>));
     attr_set = true;
   }
-  hipLaunchKernelGGL(kern, grid, dim3(64 * FQ_WAVES), sizeof(FusedLds), st, (const bf16_t*)x, (const bf16_t*)w, b, aux,
+  hipLaunchKernelGGL(kern, grid, dim3(FQ<CW>::NTHR), sizeof(FusedLds<CW>), st, (const bf16_t*)x, (const bf16_t*)w, b, aux,
                      (bf16_t*)out, (bf16_t*)qkv, g, scale, p_drop, (uint64_t)seed, seed_dev, (uint32_t*)keep,
                      (const bf16_t*)wp, bp, (bf16_t*)o_out);
 }
 
-template <typename T, bool PROJ>
+template <typename T, int CW, bool PROJ>
 void launch_fq4(dim3 grid, const void* x, const void* w, const float* b, const Aux& aux, void* out, void* qkv, Geom g,
                 float scale, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, void* keep,
                 const void* wp, const float* bp, void* o_out, hipStream_t st) {
   const bool drop = p_drop > 0.f;
-  if (drop && qkv) launch_fq<T, true, true, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
-  else if (drop) launch_fq<T, true, false, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
-  else if (qkv) launch_fq<T, false, true, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
-  else launch_fq<T, false, false, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
+  if (drop && qkv) launch_fq<T, CW, true, true, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
+  else if (drop) launch_fq<T, CW, true, false, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
+  else if (qkv) launch_fq<T, CW, false, true, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
+  else launch_fq<T, CW, false, false, PROJ>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
+}
+
+template <typename T, int CW>
+void launch_fq_width(dim3 grid, const void* x, const void* w, const float* b, const Aux& aux, void* out, void* qkv,
+                     Geom g, float scale, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
+                     void* keep, const void* wp, const float* bp, void* o_out, hipStream_t st) {
+  if (wp) launch_fq4<T, CW, true>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, wp, bp, o_out, st);
+  else launch_fq4<T, CW, false>(grid, x, w, b, aux, out, qkv, g, scale, p_drop, seed, seed_dev, keep, nullptr, nullptr,
+                                nullptr, st);
 }
 
 }  // namespace
 
 extern "C" {
 
-// Whether msu_win_attn_qkv_fwd covers a block of width C with nh heads (16-bit only).
-int msu_win_attn_qkv_supported(int C, int nh) { return C == FQ_C && nh == FQ_NH ? 1 : 0; }
+// Whether msu_win_attn_qkv_fwd covers a block of width C with nh heads (16-bit only): the two
+// stage-0 widths, C = 96 with 3 heads (Swin-T/S) and C = 128 with 4 heads (Swin-B).
+int msu_win_attn_qkv_supported(int C, int nh) {
+  return (C == 96 && nh == FQ<96>::NH) || (C == 128 && nh == FQ<128>::NH) ? 1 : 0;
+}
 
 // Fused qkv Linear + window attention (stage 0): out[B,H,W,C] = attention(x W_qkv^T + b_qkv);
 // x = LN1 rows [B,H,W,C] 16-bit, W_qkv [3C][C] 16-bit, b_qkv f32; qkv_out [B,H,W,3C] (x W^T + b,
 // what the qkv Linear would store) or null; keep / dropout / seeds and the aux workspace
-// (msu_win_attn_fwd_workspace) as msu_win_attn_fwd.
+// (msu_win_attn_fwd_workspace) as msu_win_attn_fwd.  -2 before any launch for a dtype, a (C, nh)
+// or a tensor size (B H W 3C >= 2^32) it does not cover.
 int msu_win_attn_qkv_fwd2(int dtype, const void* x, const void* w_qkv, const float* b_qkv, const float* table,
                           const void* w_proj, const float* b_proj, void* out, void* o_out, void* qkv_out, void* keep,
                           float* workspace, int B, int H, int W, int C, int nh, int shift, float p_drop,
@@ -1311,10 +1477,10 @@ int msu_win_attn_qkv_fwd2(int dtype, const void* x, const void* w_qkv, const flo
   MSU_DISPATCH16(dtype, T,
     hipLaunchKernelGGL(aux_kernel<T>, dim3((nh * 4096 + 255) / 256), dim3(256), 0, st, table, b_qkv, nh, 3 * C,
                        1.0f / scale, img, brow, zrow);
-    if (w_proj) launch_fq4<T, true>(grid, x, w_qkv, b_qkv, aux, out, qkv_out, g, scale, p_drop, seed, seed_dev, keep,
-                                    w_proj, b_proj, o_out, st);
-    else launch_fq4<T, false>(grid, x, w_qkv, b_qkv, aux, out, qkv_out, g, scale, p_drop, seed, seed_dev, keep,
-                              nullptr, nullptr, nullptr, st));
+    if (C == 128) launch_fq_width<T, 128>(grid, x, w_qkv, b_qkv, aux, out, qkv_out, g, scale, p_drop, seed, seed_dev,
+                                          keep, w_proj, b_proj, o_out, st);
+    else launch_fq_width<T, 96>(grid, x, w_qkv, b_qkv, aux, out, qkv_out, g, scale, p_drop, seed, seed_dev, keep,
+                                w_proj, b_proj, o_out, st));
   return MSU_CHECK_LAUNCH();
 }
 

@@ -812,9 +812,11 @@ def window_attention(qkv, qkv_bias, table, num_heads, shift, p_drop=0.0, seed=0,
 # Stage-0 fused unit (csrc/window_attention_mfma.hip attn_qkv_fwd_mfma): the qkv Linear and the
 # window attention in one kernel, qkv never read back (in inference never written).  The backward
 # is the existing ones in sequence: the proj Linear's, the attention backward (dqkv, relative
-# table, padded-token bias share), then the qkv Linear's (one-pass msu_linear_bwd at stage 0).
-# The kernel is the window-per-workgroup one with proj inside (msu_win_attn_qkv_fwd2);
-# MSU_ATTN_QKV=0: the unfused qkv Linear + window_attention + proj path.  (A head-stationary
+# table, padded-token bias share), then the qkv Linear's (one-pass msu_linear_bwd at C = 96; at
+# C = 128 msu_linear_bwd_supported is false and both Linear backwards are the two-kernel path).
+# The kernel is the window-per-workgroup one with proj inside (msu_win_attn_qkv_fwd2), built for
+# C = 96 / 3 heads and C = 128 / 4 heads;
+# MSU_ATTN_QKV=0: the unfused qkv Linear + window_attention + proj path at both.  (A head-stationary
 # form with independent waves, proj a separate Linear, was slower: r04d 165.6 / 165.8 vs 166.4 /
 # 166.5 img/s, gone.)
 _ATTN_QKV = switches.on("MSU_ATTN_QKV")
@@ -914,7 +916,8 @@ _window_attention_qkv = _define(
 
 
 def window_attention_qkv_fusable(x, num_heads, bias):
-    """Whether the fused stage-0 unit takes this block: 16-bit, C = 96 with 3 heads, a qkv bias."""
+    """Whether the fused stage-0 unit takes this block: 16-bit, a qkv bias, and a width the library
+    builds it for (C = 96 with 3 heads, C = 128 with 4: msu_win_attn_qkv_supported)."""
     if not _ATTN_QKV or bias is None or not x.is_cuda or act_dtype() not in _LOW:
         return False
     C = x.shape[-1]

@@ -15,8 +15,8 @@ SWITCHES = {
                          "DESIGN 4c"),
     "MSU_WGRAD_SIDE": ("1", "0: every weight gradient on the main stream (determinism bisection)",
                        "DESIGN 4b, 7 (side stream +1.6 %)"),
-    "MSU_ATTN_QKV": ("1", "0: the unfused stage-0 qkv Linear + window attention + proj",
-                     "DESIGN 4d (r04c: +0.8 %)"),
+    "MSU_ATTN_QKV": ("1", "0: the unfused stage-0 qkv Linear + window attention + proj (C = 96 and C = 128)",
+                     "DESIGN 4d (r04c: +0.8 % on Swin-T), 7 round 10 (r10a: +0.6 % on Swin-B)"),
     "MSU_GEMM_ROUTE": ("", "force a GEMM route: lib (hipBLASLt) / tok / nt",
                        "DESIGN 7 (r03c: hand-written +2.7 % over hipBLASLt)"),
     "MSU_NT_PP": ("0", "1: the ping-pong NT GEMM (gemm_pp.h) where it tiles exactly, else the persistent one",
