@@ -217,6 +217,12 @@ int msu_linear_wgrad(int dtype, const void* dY, const void* X, float* dW, float*
  * columns of the weight's gradient. */
 int msu_linear_wgrad_ld(int dtype, const void* dY, const void* X, float* dW, long ldw, float* db,
                         float* workspace, long M, int N, int K, int accumulate, void* stream);
+/* The kernel msu_linear_wgrad_ld launches for (dtype, M, N, K), no HIP call: out6 = {wave tile in
+ * units of 16 (6 / 8: the 16-bit wave kernel; 0: the generic kernel), waves along N, waves along K,
+ * rows per LDS stage (32 per row-wave; 64 generic), splits S of the M range, rows per split (a
+ * multiple of the stage rows; S * rows per split >= M, trailing splits may be empty)}.
+ * Returns 0, or -2 where msu_linear_wgrad_ld would. */
+int msu_linear_wgrad_plan(int dtype, long M, int N, int K, int* out6);
 
 /* ---------------------------------------------------------------- Linear backward in one pass
  * Stage-0 Linears of the Swin block (qkv, proj, mlp.0, mlp.3; model_parts.py:143-151, called at

@@ -419,12 +419,24 @@ void launch_wave(dim3 grid, const bf16_t* dY, const bf16_t* X, float* part, floa
   }
 }
 
+// rows per split: M over S splits, rounded up to whole stages of `rows` rows (trailing splits
+// may end up empty: they write zero slabs)
+inline long split_rows(long M, int S, int rows) {
+  const long mchunk = (M + S - 1) / S;
+  return (mchunk + rows - 1) / rows * rows;
+}
+
+// rows per LDS stage of the wave kernel: 32 per row-wave
+inline int wave_stage_rows(const WavePlan& p) {
+  const int nw = p.wn * p.wk == 3 ? 3 : 4;
+  return 32 * (nw / (p.wn * p.wk));
+}
+
 template <typename T>
 int run_wave(const WavePlan& p, const bf16_t* dY, const bf16_t* X, float* part, float* dbpart, long M, int N, int K,
              hipStream_t st) {
-  const int wt = 16 * p.ntw, nw = p.wn * p.wk == 3 ? 3 : 4, wm = nw / (p.wn * p.wk), rs = 32 * wm;
-  long mchunk = (M + p.S - 1) / p.S;
-  mchunk = (mchunk + rs - 1) / rs * rs;
+  const int wt = 16 * p.ntw;
+  const long mchunk = split_rows(M, p.S, wave_stage_rows(p));
   const int ntiles = (N / (p.wn * wt)) * (K / (p.wk * wt));
   const dim3 grid((unsigned)(ntiles * p.S));
 #define MSU_WAVE(NTW, WN, WK)                                                                                        \
@@ -498,8 +510,7 @@ int msu_linear_wgrad_ld(int dtype, const void* dY, const void* X, float* dW, lon
     }
   }
   const int S = pick_splits(M, N, K);
-  long mchunk = (M + S - 1) / S;
-  mchunk = (mchunk + BM - 1) / BM * BM;
+  const long mchunk = split_rows(M, S, BM);
   float* part = workspace;
   float* dbpart = db ? workspace + (long)S * N * K : nullptr;
   const int bt = tile_of(N, K);
@@ -514,6 +525,24 @@ int msu_linear_wgrad_ld(int dtype, const void* dY, const void* X, float* dW, lon
   const ColSeg segs[2] = {{part, (long)N * K, (long)N * K, dW, K, ldw}, {dbpart, N, N, db}};
   colsum_multi(segs, db ? 2 : 1, S, accumulate, st);
   return MSU_CHECK_LAUNCH();
+}
+
+// The kernel msu_linear_wgrad_ld launches for (dtype, M, N, K), by the launcher's own arithmetic:
+// out = {wave tile in 16s (0: generic kernel), waves along N, waves along K, rows per LDS stage,
+// splits, rows per split}.  No HIP call.
+int msu_linear_wgrad_plan(int dtype, long M, int N, int K, int* out) {
+  if (N % 8 || K % 8 || M < 0) return -2;
+  WavePlan p;
+  if (msu_is16(dtype)) p = wave_plan(M, N, K);
+  const int rows = p.ntw ? wave_stage_rows(p) : BM;
+  const int S = p.ntw ? p.S : pick_splits(M, N, K);
+  out[0] = p.ntw;
+  out[1] = p.ntw ? p.wn : 1;
+  out[2] = p.ntw ? p.wk : 1;
+  out[3] = rows;
+  out[4] = S;
+  out[5] = (int)split_rows(M, S, rows);
+  return 0;
 }
 
 int msu_linear_wgrad(int dtype, const void* dY, const void* X, float* dW, float* db, float* workspace,
