@@ -286,6 +286,10 @@ MSU_DEV const void* zero_src(int slot) { return g_zero_region + 4 * (slot & 255)
 
 #define MSU_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -1)
 
+// compute units of the current device (the grid of the persistent kernels), read once per
+// process; 256 where the query fails.  Defined in gemm_nt.hip.
+int msu_num_cus();
+
 // ------------------------------------------------------------------ tile queues
 // Persistent kernels beside the side stream: a workgroup takes its first
 // tile statically and claims the others from a device counter, so workgroups that get a CU late

@@ -1721,16 +1721,6 @@ int g_conv_dyn = 1;
 // widths other than 96 take the generic kernels
 int g_conv_generic_wide = 0;
 
-int num_cus() {
-  static int n = 0;
-  if (n <= 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <typename T, int NCT, int KS, int NW, int MT, bool WDB, bool IN_D2S, bool IN_GELU, bool OUT_D2S,
           bool OUT_GGRAD, bool BIAS, bool DUAL>
 int launch_v2(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S,
@@ -1748,7 +1738,7 @@ int launch_v2(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float*
   if (ntiles == 0) return 0;
   // 32-bit element offsets inside the kernel
   if ((long)g.B * g.H * g.W * (g.Cin > g.Cout ? g.Cin : g.Cout) >= (1L << 31)) return -2;
-  const int grid = (int)(ntiles < num_cus() ? ntiles : num_cus());
+  const int grid = (int)(ntiles < msu_num_cus() ? ntiles : msu_num_cus());
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, X, Wt, bias, S, Y, Y2, g, (int)ntiles);
   return MSU_CHECK_LAUNCH();
 }
@@ -1769,7 +1759,7 @@ int launch_v3s(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  const int grid = (int)(ntiles < num_cus() ? ntiles : num_cus());
+  const int grid = (int)(ntiles < msu_num_cus() ? ntiles : msu_num_cus());
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * G::NW), lds, st, X, Wt, bias, S, Y, Y2, g, (int)ntiles,
                      g_conv_dyn ? tile_queue(st) : nullptr);
   return MSU_CHECK_LAUNCH();

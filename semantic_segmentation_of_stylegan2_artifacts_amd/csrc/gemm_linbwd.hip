@@ -458,20 +458,10 @@ constexpr size_t linbwd_lds() {
   return sizeof(bf16_t) * ((size_t)K * (N + 8) + 2 * (size_t)ts_of(K, N) * ((N + 8) + ldx_of<K>()));
 }
 
-int num_cus_lb() {
-  static const int cus = [] {
-    int n = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 long grid_of(long M, int K, int N) {
   const int ts = ts_of(K, N);
   const long ntiles = (M + ts - 1) / ts;
-  const long g = num_cus_lb();
+  const long g = msu_num_cus();
   return ntiles < g ? ntiles : g;
 }
 

@@ -478,8 +478,6 @@ int g_nt_a3 = 0;
 // round trip costs 2-3 us on the short stage-2/3 launches and the step did not gain, r06q/r06r)
 int g_nt_dyn = 0;
 
-int num_cus_nt();
-
 // BN of the ping-pong kernel for this shape, or 0 (gemm_nt_kernel takes it): exact tiling, and
 // rounds of tiles at least 3/4 full (the stage-3 shapes, 96-288 tiles of 256 rows on 256 CUs,
 // keep the persistent kernel's 128-row tiles)
@@ -491,23 +489,13 @@ int pp_bn(long M, int N, int K, int epi, bool wkn) {
   int bn = 0;
   if (N % 192 == 0) bn = 192;
   if (!bn) return 0;
-  const long tiles = (M / pp::BM) * (N / bn), cus = num_cus_nt();
+  const long tiles = (M / pp::BM) * (N / bn), cus = msu_num_cus();
   const long rounds = (tiles + cus - 1) / cus;
   return 4 * tiles >= 3 * rounds * cus ? bn : 0;
 }
 
 bool nt_shape_ok(long M, int N, int K) {
   return M > 0 && M < (1L << 31) && N > 0 && N % 32 == 0 && K > 0 && K % 64 == 0 && (long)M * N < (1L << 40);
-}
-
-int num_cus_nt() {
-  static const int cus = [] {
-    int n = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
 }
 
 // Tile configuration of a shape, by a rounds-of-tiles cost model: the output is covered in
@@ -530,7 +518,7 @@ NtCfg nt_cfg(long M, int N, bool wkn) {
   if (g_nt_force == 1 && !wkn && N % 192 == 0) return NtCfg{2, 192};
   if (g_nt_force == 2) return NtCfg{4, 128};
   if (g_nt_force == 3) return NtCfg{2, 128};
-  const long cus = num_cus_nt();
+  const long cus = msu_num_cus();
   const NtCfg cands[4] = {{4, 128}, {2, 128}, {4, 192}, {2, 192}};
   NtCfg best = cands[0];
   double best_cost = -1.0;
@@ -557,7 +545,7 @@ NtCfg nt_cfg(long M, int N, bool wkn) {
 template <typename T, int WM, int NST, bool WKN, int BNT, int KB = 64>
 void launch_nt(int epi, const NtArgs& a, hipStream_t st) {
   const long tiles = (long)a.tiles_m * a.tiles_n;
-  const long cap = (long)num_cus_nt() * (WM == 2 ? 2 : 1);
+  const long cap = (long)msu_num_cus() * (WM == 2 ? 2 : 1);
   const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
   const dim3 blk(128 * WM);
   NtArgs q = a;
@@ -600,7 +588,7 @@ int nt_launch(int dtype, const void* A, const void* W, const float* bias, void* 
     a.tiles_n = N / pbn;
     a.tiles_m = (int)(M / pp::BM);
     const long tiles = (long)a.tiles_m * a.tiles_n;
-    const unsigned grid = (unsigned)(tiles < num_cus_nt() ? tiles : num_cus_nt());
+    const unsigned grid = (unsigned)(tiles < msu_num_cus() ? tiles : msu_num_cus());
     MSU_DISPATCH16(dtype, T,
       if (epi == EPI_PLAIN) hipLaunchKernelGGL((pp::gemm_pp_kernel<T, EPI_PLAIN, 192>), dim3(grid), dim3(512), 0, st, a);
       else hipLaunchKernelGGL((pp::gemm_pp_kernel<T, EPI_GELU_DUAL, 192>), dim3(grid), dim3(512), 0, st, a));
@@ -622,6 +610,17 @@ int nt_launch(int dtype, const void* A, const void* W, const float* bias, void* 
 }
 
 }  // namespace
+
+// the library's one CU count (common.h): every persistent kernel's launcher sizes its grid by it
+int msu_num_cus() {
+  static const int cus = [] {
+    int n = 0, dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    return n;
+  }();
+  return cus;
+}
 
 extern "C" {
 

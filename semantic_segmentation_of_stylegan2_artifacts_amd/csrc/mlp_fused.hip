@@ -272,16 +272,6 @@ __global__ void __launch_bounds__(64 * MW) mlp_fused_kernel(MlpArgs A) {
   }
 }
 
-int num_cus_mlp() {
-  static const int cus = [] {
-    int n = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 template <typename T, bool H_OUT, bool LN_IN = false>
 int launch_mlp(const MlpArgs& a, hipStream_t st) {
   auto kern = mlp_fused_kernel<T, H_OUT, LN_IN>;
@@ -294,7 +284,7 @@ int launch_mlp(const MlpArgs& a, hipStream_t st) {
     attr_set = true;
   }
   const long ntiles = (M + MT - 1) / MT;
-  long grid = num_cus_mlp();
+  long grid = msu_num_cus();
   if (grid * MW > ntiles) grid = (ntiles + MW - 1) / MW;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MW), sizeof(MlpLds), st, a);
   return MSU_CHECK_LAUNCH();

@@ -1398,16 +1398,6 @@ __global__ void __launch_bounds__(FQ<CW>::NTHR) attn_qkv_fwd_mfma(const bf16_t* 
   }
 }
 
-int num_cus_fq() {
-  static const int cus = [] {
-    int n = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 template <typename T, int CW, bool DROP, bool STORE_QKV, bool PROJ>
 void launch_fq(dim3 grid, const void* x, const void* w, const float* b, const Aux& aux, void* out, void* qkv, Geom g,
                float scale, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, void* keep,
@@ -1471,7 +1461,7 @@ int msu_win_attn_qkv_fwd2(int dtype, const void* x, const void* w_qkv, const flo
   const float scale = 1.0f / sqrtf((float)HD);
   float* img; bf16_t* brow; bf16_t* zrow;
   const Aux aux = carve_aux(workspace, C, nh, &img, &brow, &zrow);
-  const long nb = g.nwin < num_cus_fq() ? g.nwin : num_cus_fq();
+  const long nb = g.nwin < msu_num_cus() ? g.nwin : msu_num_cus();
   const dim3 grid((unsigned)nb);
   if ((w_proj == nullptr) != (b_proj == nullptr)) return -3;
   MSU_DISPATCH16(dtype, T,

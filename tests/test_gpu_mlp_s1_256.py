@@ -8,6 +8,12 @@ H held to the same bound; gradients within 3e-2 of the reference's largest entry
 formats.  "wrap" is M = 128 (CUs + 1) + 5, the smallest M at which a workgroup walks a second
 128-token tile: the weight ring and the hand-over parity continue across the tile boundary, the
 next tile's x is loaded behind the last fc1, and the last tile is ragged.
+
+The last three properties (exact H and equal y rows, nothing written past M, two launches bit for
+bit) guard code that both kernels of csrc/mlp_s1.hip share (the phases of ``S1Wave``, the ring
+bookkeeping of ``S1Ring``), so the ``*_one_role`` tests hold the one-role widths (128 -> 512 and
+192 -> 768, ``mlp_s1_kernel``, 256-token workgroup tiles) to them too, at the same M relative to
+the tile: TT + 1 and the wrap TT (CUs + 1) + 5.
 """
 import pytest
 import torch
@@ -29,27 +35,32 @@ def low(request):
     return request.param
 
 
-def _m(M):
+ONE_ROLE = [128, 192]  # the widths of mlp_s1_kernel; their workgroup tile:
+TT1 = 256
+
+
+def _m(M, TT=128):
     if M == "wrap":
-        return 128 * (torch.cuda.get_device_properties(0).multi_processor_count + 1) + 5
+        return TT * (torch.cuda.get_device_properties(0).multi_processor_count + 1) + 5
     return M
 
 
 _PARAMS = {}
 
 
-def _params(seed=11):
-    """f32 master parameters, made once per seed and never modified."""
-    if seed not in _PARAMS:
+def _params(seed=11, C=C):
+    """f32 master parameters, made once per seed and width and never modified."""
+    HD = 4 * C
+    if (seed, C) not in _PARAMS:
         g = torch.Generator().manual_seed(seed)
-        _PARAMS[seed] = ((torch.randn(HD, C, generator=g) / C ** 0.5).to(DEV),
-                         (torch.randn(HD, generator=g) * 0.1).to(DEV),
-                         (torch.randn(C, HD, generator=g) / HD ** 0.5).to(DEV),
-                         (torch.randn(C, generator=g) * 0.1).to(DEV))
-    return _PARAMS[seed]
+        _PARAMS[seed, C] = ((torch.randn(HD, C, generator=g) / C ** 0.5).to(DEV),
+                            (torch.randn(HD, generator=g) * 0.1).to(DEV),
+                            (torch.randn(C, HD, generator=g) / HD ** 0.5).to(DEV),
+                            (torch.randn(C, generator=g) * 0.1).to(DEV))
+    return _PARAMS[seed, C]
 
 
-def _x(M, low, seed=1):
+def _x(M, low, seed=1, C=C):
     return torch.randn(M, C, generator=torch.Generator().manual_seed(M + seed)).to(DEV, low)
 
 
@@ -69,8 +80,9 @@ def _within(name, a, r):
 
 def _fwd_raw(x, w1l, b1, w2l, b2, y, h, M):
     """msu_mlp_fused_fwd itself on the given buffers (h may be None)."""
+    C = x.shape[1]
     _lib.call("msu_mlp_fused_fwd", ops._dt(x), ops._p(x), ops._p(w1l), ops._p(b1), ops._p(w2l), ops._p(b2),
-              ops._p(y), ops._p(h), M, C, HD, ops._s(x))
+              ops._p(y), ops._p(h), M, C, 4 * C, ops._s(x))
 
 
 def test_width_is_shipped_and_routed():
@@ -140,8 +152,8 @@ def test_gradients_match_fp32(M, low, monkeypatch):
         assert err <= 3e-2 * r.abs().max().item(), f"{name} M={M}: {err:.3e} vs {r.abs().max().item():.3e}"
 
 
-def _distinct_b1(low):
-    """1024 distinct values exactly representable in `low`, 2^-7 .. 2, alternating sign."""
+def _distinct_b1(low, HD=HD):
+    """HD distinct values exactly representable in `low`, 2^-7 .. 2, alternating sign."""
     base, step = (0x3C00, 1) if low == torch.bfloat16 else (0x2000, 8)
     bits = (base + step * torch.arange(HD, dtype=torch.int32)).to(torch.int16)
     v = bits.view(low).float()
@@ -150,15 +162,14 @@ def _distinct_b1(low):
     return v.to(DEV)
 
 
-@pytest.mark.parametrize("M", [129, "wrap"])
-def test_hand_over_is_exact(M, low):
+def _check_h_is_exact(M, low, C):
     """x = 0: fc1 adds nothing, so every stored H row is round16(b1) = b1 bit for bit, whatever
     the MFMA numerics: a wrong hidden-unit permutation or chunk order shows.  With W1 = 0 and
     b2 = 0 too, every token sees the same GELU(H) row: all y rows are bitwise equal and match
     the reference's row, which a stale or swapped hand-over buffer (wrong parity) breaks."""
-    M = _m(M)
-    w1, _, w2, _ = _params()
-    b1 = _distinct_b1(low)
+    HD = 4 * C
+    w1, _, w2, _ = _params(C=C)
+    b1 = _distinct_b1(low, HD)
     x = torch.zeros(M, C, device=DEV, dtype=low)
     w1l, w2l = w1.to(low).contiguous(), w2.to(low).contiguous()
     b2z = torch.zeros(C, device=DEV)
@@ -171,16 +182,27 @@ def test_hand_over_is_exact(M, low):
     assert torch.equal(h.view(torch.int16), want.expand(M, HD))
     assert torch.equal(y.view(torch.int16), y[:1].view(torch.int16).expand(M, C)), "y rows differ from each other"
     yr, _ = _ref(x[:1], torch.zeros_like(w1), b1, w2, b2z, low)
-    _within(f"y row M={M}", y[:1], yr)
+    _within(f"y row C={C} M={M}", y[:1], yr)
 
 
-@pytest.mark.parametrize("M", [1, 33, 129, 1000])
-def test_nothing_is_written_past_m(M, low):
+@pytest.mark.parametrize("M", [129, "wrap"])
+def test_hand_over_is_exact(M, low):
+    _check_h_is_exact(_m(M), low, C)
+
+
+@pytest.mark.parametrize("M", [TT1 + 1, "wrap"])
+@pytest.mark.parametrize("width", ONE_ROLE)
+def test_h_is_exact_one_role(width, M, low):
+    _check_h_is_exact(_m(M, TT1), low, width)
+
+
+def _check_nothing_is_written_past_m(M, low, C):
     """y and h are the first M rows of larger buffers filled with a sentinel bit pattern: the
-    rows from M on (more than a whole workgroup tile of them) are untouched."""
-    w1, b1, w2, b2 = _params()
+    160 rows from M on are untouched, with and without H."""
+    HD = 4 * C
+    w1, b1, w2, b2 = _params(C=C)
     w1l, w2l = w1.to(low).contiguous(), w2.to(low).contiguous()
-    x = _x(M, low)
+    x = _x(M, low, C=C)
     extra, sentinel = 160, 0x5A5A
     ybuf = torch.full((M + extra, C), sentinel, device=DEV, dtype=torch.int16)
     hbuf = torch.full((M + extra, HD), sentinel, device=DEV, dtype=torch.int16)
@@ -196,12 +218,24 @@ def test_nothing_is_written_past_m(M, low):
     _within(f"y no-H M={M}", ybuf[:M].view(low), yr)
 
 
-def test_two_launches_agree_bitwise(low):
-    """The same inputs twice at the wrap M: y and H bit for bit (a hand-over race would differ)."""
-    M = _m("wrap")
-    w1, b1, w2, b2 = _params()
+@pytest.mark.parametrize("M", [1, 33, 129, 1000])
+def test_nothing_is_written_past_m(M, low):
+    _check_nothing_is_written_past_m(M, low, C)
+
+
+@pytest.mark.parametrize("M", [1, 33, TT1 + 1, 1000])
+@pytest.mark.parametrize("width", ONE_ROLE)
+def test_nothing_is_written_past_m_one_role(width, M, low):
+    _check_nothing_is_written_past_m(M, low, width)
+
+
+def _check_two_launches_agree_bitwise(M, low, C):
+    """The same inputs twice at the wrap M: y and H bit for bit (a hand-over race, a read ahead
+    of its DMA or a slot refilled under a reader would differ)."""
+    HD = 4 * C
+    w1, b1, w2, b2 = _params(C=C)
     w1l, w2l = w1.to(low).contiguous(), w2.to(low).contiguous()
-    x = _x(M, low)
+    x = _x(M, low, C=C)
     out = []
     for _ in range(2):
         y = torch.empty(M, C, device=DEV, dtype=low)
@@ -211,3 +245,12 @@ def test_two_launches_agree_bitwise(low):
     torch.cuda.synchronize()
     assert torch.equal(out[0][0].view(torch.int16), out[1][0].view(torch.int16))
     assert torch.equal(out[0][1].view(torch.int16), out[1][1].view(torch.int16))
+
+
+def test_two_launches_agree_bitwise(low):
+    _check_two_launches_agree_bitwise(_m("wrap"), low, C)
+
+
+@pytest.mark.parametrize("width", ONE_ROLE)
+def test_two_launches_agree_bitwise_one_role(width, low):
+    _check_two_launches_agree_bitwise(_m("wrap", TT1), low, width)
