@@ -1257,35 +1257,67 @@ __global__ void __launch_bounds__(64 * NT) conv3x3_wgrad_kernel(const T* __restr
   if (dy == 0 && tid < g.Cout) dbpart[(long)chunk * g.Cout + tid] = dbacc;
 }
 
-// ------------------------------------------------------------------ bf16 wgrad, v2
-// Persistent weight gradient for CinP = Cout = 96 on v_mfma_f32_16x16x32_bf16.  One
-// 12-wave workgroup per CU (3 waves per SIMD) owns all 9 x 96 x 96 accumulators for its
-// share of the pixels: wave w = (dy = w/4, co half, ci half) holds 3 dx x 3 co-tiles x
-// 3 ci-tiles = 27 16x16 tiles (108 registers).  Per pixel tile (4 rows x 32 pixels) the
-// input halo [(4+2) x 34][ci] and the dY tile [128][co] sit in LDS (pixel stride 104
-// elements); both operands are read k-strided (k = pixels) with ds_read_b64_tr_b16.
-// Staging is LDS-DMA (global_load_lds_dwordx4) into the other of two LDS buffers while the
-// current tile is multiplied: the image is 13 16-B slots per pixel (12 data + 1 pad) filled
-// lane-linearly; pad slots and out-of-image pixels read a 16-B zero block.  After its own
-// DMAs land (vmcnt), each wave GELU-converts the halo slots it wrote, in place, so no
-// registers are held across the tile and no extra barrier is needed.
-// Partials: [block][dy][co][dx][ci] + db [block][co], the layout wgrad_reduce_kernel sums.
-template <typename T, bool IN_D2S, bool IN_GELU>
+// ------------------------------------------------------------------ 16-bit wgrad, v2
+// Persistent weight gradient for CinP = Cout = C (96, 128) on v_mfma_f32_16x16x32.  One
+// 12-wave workgroup per CU (3 waves per SIMD) owns the accumulators of all nine taps of COB
+// output channels x C input channels for its share of the pixels: wave w = (dy = w/4, co half,
+// ci half) holds 3 dx x NI co-tiles x NJ ci-tiles of 16 x 16.  Per pixel tile (4 rows x 32
+// pixels) the input halo [(4+2) x 34][C] and the dY tile [128][COB] sit in LDS, each padded to
+// an odd number of 16-B slots per pixel (WG2 below); both operands are read k-strided
+// (k = pixels) with ds_read_b64_tr_b16.  Staging is LDS-DMA (global_load_lds_dwordx4) into the
+// other of two LDS buffers while the current tile is multiplied: the X image and then the dY
+// image are filled lane-linearly, slot by slot; pad slots and out-of-image pixels read a 16-B
+// zero block.  After its own DMAs land (vmcnt), each wave GELU-converts the halo slots it
+// wrote, in place, so no registers are held across the tile and no extra barrier is needed.
+//   C = 96: COB = 96, 3 x 3 tiles per dx (108 accumulator registers), both images at a pixel
+//   stride of 104 elements (13 slots).  Block s takes the tiles s, s + gridDim.x, ...
+//   C = 128: all nine taps of 128 x 128 are 576 KB of f32 accumulators, more than a CU's
+//   register file, so a workgroup owns one HALF of the output channels (COB = 64, SPLIT = 2):
+//   block 2 s + h takes the tiles of pixel share s (s, s + nshare, ...) and co 64 h .. 64 h + 63,
+//   2 x 4 tiles per dx (96 registers); X at a stride of 136 (17 slots), the block's dY half-tile
+//   at 72 (9 slots).  Each X band is staged by the two blocks of a share.
+// Partials: chunk s of [chunk][dy][co][dx][ci] + db [chunk][co], each block writing its COB co
+// rows: the layout colsum_multi sums, deterministically, over nshare chunks.
+template <int C_>
+struct WG2 {
+  static_assert(C_ == 96 || C_ == 128, "widths with a register plan");
+  static constexpr int C = C_;
+  static constexpr int COB = C == 96 ? 96 : 64, SPLIT = C / COB;  // co per workgroup, workgroups per pixel share
+  static constexpr int TH = 4, TWV = 32, NW = 12, HWD = TWV + 2;
+  static constexpr int NI = COB / 32, NJ = C / 32;  // 16-wide co / ci tiles per wave
+  static constexpr int PSX = C + 8, SLX = PSX / 8;      // X image: pixel stride, 16-B slots per pixel (1 pad)
+  static constexpr int PSD = COB + 8, SLD = PSD / 8;    // dY image
+  static constexpr int HPIX = (TH + 2) * HWD;    // 204 halo pixels
+  static constexpr int DPIX = TH * TWV;          // 128 dY pixels
+  static constexpr int XSLOT = HPIX * SLX;       // slots of the X image; the dY image follows
+  static constexpr int NSLOT = XSLOT + DPIX * SLD;
+  static constexpr int NINS = (NSLOT + 63) / 64;  // DMA wave-instructions per tile
+  static constexpr int PER_WAVE = (NINS + NW - 1) / NW;
+  static constexpr int BUF = NINS * 64 * 8;      // elements per LDS buffer (covers the overrun)
+  static constexpr size_t LDS = 2 * sizeof(bf16_t) * (size_t)BUF;
+  static_assert(LDS <= 160 * 1024, "LDS");
+  static_assert(2 * ((3 * HWD + 2) * PSX + 16 * (NJ - 1) + 32 * PSX) < 65536 &&
+                    2 * (3 * TWV * PSD + 16 * (NI - 1) + 32 * PSD) < 65536 && 2 * 16 * PSD * (DPIX / 16 - 1) < 65536,
+                "fragment and bias read offsets are immediates");
+  // A half-wave's k-strided read touches the 8 pixels of one parity, 32 B (8 banks) each.  Pixels
+  // two apart are PS dwords apart, so the 8 spans are the multiples 0 .. 7 of PS mod 64 banks:
+  // all 64 banks once iff PS = 8 * odd (104 = 8 * 13, 136 = 8 * 17, 72 = 8 * 9).
+  static_assert(PSX % 16 == 8 && PSD % 16 == 8, "pixels of one parity on distinct 32-B bank spans");
+  // slot ch0 of a pixel's sl slots -> its 16-B chunk; the pad slot re-reads chunk 0
+  static MSU_DEV int chunk(int ch0, int sl) { return ch0 < sl - 1 ? ch0 : 0; }
+};
+
+template <typename T, int C, bool IN_D2S, bool IN_GELU>
 __global__ void __launch_bounds__(768) conv3x3_wgrad_v2_kernel(const bf16_t* __restrict__ X,
                                                                const bf16_t* __restrict__ DY,
                                                                float* __restrict__ part,
                                                                float* __restrict__ dbpart, ConvGeom g,
                                                                int ntiles) {
-  constexpr int C = 96, TH = 4, TWV = 32, NW = 12;
-  constexpr int PS = C + 8;                  // LDS pixel stride (both images), 13 slots
-  constexpr int SLOTS = PS / 8;
-  constexpr int HWD = TWV + 2;
-  constexpr int HPIX = (TH + 2) * HWD;       // 204 halo pixels
-  constexpr int DPIX = TH * TWV;             // 128 dY pixels
-  constexpr int NSLOT = (HPIX + DPIX) * SLOTS;
-  constexpr int NINS = (NSLOT + 63) / 64;    // DMA wave-instructions per tile
-  constexpr int PER_WAVE = (NINS + NW - 1) / NW;
-  constexpr int BUF = NINS * 64 * 8;         // elements per LDS buffer (covers the overrun)
+  using G = WG2<C>;
+  constexpr int COB = G::COB, SPLIT = G::SPLIT, TH = G::TH, TWV = G::TWV, NW = G::NW, HWD = G::HWD;
+  constexpr int NI = G::NI, NJ = G::NJ, PSX = G::PSX, SLX = G::SLX, PSD = G::PSD, SLD = G::SLD;
+  constexpr int HPIX = G::HPIX, DPIX = G::DPIX, XSLOT = G::XSLOT, NSLOT = G::NSLOT;
+  constexpr int NINS = G::NINS, PER_WAVE = G::PER_WAVE, BUF = G::BUF;
   typedef __attribute__((address_space(3))) void lds_void;
   typedef __attribute__((address_space(1))) void glb_void;
 
@@ -1294,6 +1326,7 @@ __global__ void __launch_bounds__(768) conv3x3_wgrad_v2_kernel(const bf16_t* __r
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int dy = wave >> 2, coh = (wave >> 1) & 1, cih = wave & 1;
+  const int share = blockIdx.x / SPLIT, half = blockIdx.x % SPLIT, nshare = gridDim.x / SPLIT;
   const int tiles_x = (g.W + TWV - 1) / TWV, tiles_y = (g.H + TH - 1) / TH;
   const int per_img = tiles_x * tiles_y;
 
@@ -1313,231 +1346,29 @@ __global__ void __launch_bounds__(768) conv3x3_wgrad_v2_kernel(const bf16_t* __r
       const int k = wave + NW * r;
       if (k < NINS) {
         const int s = 64 * k + ln;
-        const int pix = s / SLOTS, ch0 = s - (s / SLOTS) * SLOTS;
-        const int ch = ch0 < SLOTS - 1 ? ch0 : 0;  // pad slot: re-read chunk 0 of the pixel
         const void* src = zero_src(s);
-        if (pix < HPIX) {
+        // slot -> (pixel, 16-B chunk) of its image; the pad slot re-reads chunk 0 of the pixel.
+        // With one slot count for both images (C = 96) the dY slots continue the X image's
+        // pixels: (pix, chx) is worked out once, ahead of the branch, and serves both images
+        // (written inside the branches it is done in both: 2113 instead of 2055 instructions in
+        // the plain bf16 kernel, r13a).
+        constexpr bool ONE = SLD == SLX;
+        const int pix = s / SLX, chx = ONE ? G::chunk(s - pix * SLX, SLX) : 0;
+        if (ONE ? pix < HPIX : s < XSLOT) {
+          const int ch = ONE ? chx : G::chunk(s - pix * SLX, SLX);
           const int row = pix / HWD, col = pix - (pix / HWD) * HWD;
           const int y = y0 - 1 + row, x = x0 - 1 + col;
           if (y >= 0 && y < g.H && x >= 0 && x < g.W) src = X + pix_off32<IN_D2S>(b, y, x, g.H, g.W, C) + ch * 8;
-        } else if (pix < HPIX + DPIX) {
-          const int dp = pix - HPIX;
+        } else if (ONE ? pix < HPIX + DPIX : s < NSLOT) {
+          const int t = s - XSLOT;
+          const int dp = ONE ? pix - HPIX : t / SLD;
+          const int ch = ONE ? chx : G::chunk(t - dp * SLD, SLD);
           const int y = y0 + dp / TWV, x = x0 + dp % TWV;
-          if (y < g.H && x < g.W) src = DY + pix_off32<false>(b, y, x, g.H, g.W, C) + ch * 8;
+          if (y < g.H && x < g.W) src = DY + pix_off32<false>(b, y, x, g.H, g.W, C) + COB * half + ch * 8;
         }
         // ablation 4096: no DMA (the LDS images stay stale; results wrong)
         if constexpr (!(MSU_EXP & 4096))
           __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(lds + buf * BUF + 64 * 8 * k), 16, 0, 0);
-      }
-    }
-  };
-  // after this wave's DMAs landed: GELU the halo slots it wrote, in place
-  auto gelu_own = [&](int buf) __attribute__((always_inline)) {
-    if constexpr (IN_GELU) {
-      const int ln = opaque(lane);
-#pragma unroll
-      for (int r = 0; r < PER_WAVE; ++r) {
-        const int k = wave + NW * r;
-        const int s = 64 * k + ln;
-        if (k < NINS && s / SLOTS < HPIX && s % SLOTS < SLOTS - 1) {
-          u32x4* p = reinterpret_cast<u32x4*>(lds + buf * BUF + 8 * s);
-          *p = gelu8<T>(*p);
-        }
-      }
-    }
-  };
-
-  f32x4 acc[3][3][3];  // [dx][co tile][ci tile]
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) acc[d][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float dbacc[2] = {0.f, 0.f};
-  const int dbc = 2 * (tid % 48), dbg = tid / 48;  // channel pair, pixel group (16 groups)
-
-  int tile = blockIdx.x;
-  int cur = 0;
-  if (tile < ntiles) {
-    stage(tile, 0);
-    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) & lgkmcnt(0)
-    gelu_own(0);
-  }
-  __syncthreads();
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int next = tile + gridDim.x;
-    if (next < ntiles) stage(next, cur ^ 1);
-    const bf16_t* sX = lds + cur * BUF;
-    const bf16_t* sD = sX + HPIX * PS;
-    // All LDS reads of the tile are untracked (inline asm): a compiler-visible ds_read would
-    // be preceded by vmcnt(0) for the next tile's pending LDS-DMA and serialise the two.
-    // bias gradient: 16 groups x 48 channel pairs, 8 pixels each (ablation 65536: none)
-    if constexpr (!(MSU_EXP & 65536)) {
-      const uint32_t ba = lds_u32(sD + dbg * PS + dbc);
-      uint32_t v[DPIX / 16];
-      unroll_for<DPIX / 16>([&](auto P) {
-        v[decltype(P)::value] = ds_b32_untracked<2 * 16 * PS * decltype(P)::value>(ba);
-      });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int p = 0; p < DPIX / 16; ++p) {
-        vreg_pin(v[p]);
-        dbacc[0] += Fmt16<T>::lo(v[p]);
-        dbacc[1] += Fmt16<T>::hi(v[p]);
-      }
-    }
-    // lane part of a k-strided fragment read: pixels 2(4g + q) + half (+16 for the second
-    // half of the fragment), g = lane group within the 32-lane half, q = (lane&15)>>2,
-    // columns 4(lane&3); everything else is an immediate offset.  Same pixel order for both
-    // operands; pixels of one parity sit 104 * 2j B apart: distinct 32-B bank spans, so each
-    // half's 32 lanes hit all 64 banks once (pixels 8(lane>>4) + q: 2-way conflicts).
-    const int laneoff = opaque((2 * (4 * ((lane >> 4) & 1) + ((lane & 15) >> 2)) + (lane >> 5)) * PS + 4 * (lane & 3));
-    const uint32_t xa = lds_u32(sX + laneoff + dy * HWD * PS + 48 * cih);
-    const uint32_t da = lds_u32(sD + laneoff + 48 * coh);
-    unroll_for<TH>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      // the dY fragments of row r serve all three dx (read once per row, not once per dx:
-      // 12 instead of 18 fragment reads per 27 MFMAs -- the LDS reads bound this loop).
-      // (Reading group g + 1's X fragments before group g's MFMAs measured no faster, r06x:
-      // the loop is bound by its operand traffic, ablations r06w.)
-      bf16x8 af[3];
-      unroll_for<3>([&](auto I) {
-        constexpr int o = 2 * (r * TWV * PS + 16 * decltype(I)::value);
-        if constexpr (MSU_EXP & 32768) af[decltype(I)::value] = bf16x8{};  // ablation: no fragment reads
-        else af[decltype(I)::value] = tr8_untracked<o, o + 32 * PS>(da);
-      });
-      unroll_for<3>([&](auto D) {
-        constexpr int d = decltype(D)::value;
-        bf16x8 bf[3];
-        unroll_for<3>([&](auto J) {
-          constexpr int o = 2 * ((r * HWD + d) * PS + 16 * decltype(J)::value);
-          if constexpr (MSU_EXP & 32768) bf[decltype(J)::value] = bf16x8{};
-          else bf[decltype(J)::value] = tr8_untracked<o, o + 32 * PS>(xa);
-        });
-        if constexpr (d == 0)
-          lds_wait_tie<0>(bf[0], bf[1], bf[2], af[0], af[1], af[2]);
-        else
-          lds_wait_tie<0>(bf[0], bf[1], bf[2]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            if constexpr (MSU_EXP & 16384) asm volatile("" ::"v"(af[i]), "v"(bf[j]));  // ablation: no MFMA
-            else acc[d][i][j] = Fmt16<T>::mma16(af[i], bf[j], acc[d][i][j]);
-        __builtin_amdgcn_sched_barrier(0);
-      });
-    });
-    if (next < ntiles) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      gelu_own(cur ^ 1);
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  // partial [blk][dy][co][dx][ci]: lane holds co = co0 + 4(lane>>4) + r, ci = ci0 + (lane&15)
-  float* out = part + ((long)blockIdx.x * 3 + dy) * (long)C * 3 * C;
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int co = 48 * coh + 16 * i + 4 * (lane >> 4) + r;
-          const int ci = 48 * cih + 16 * j + (lane & 15);
-          out[((long)co * 3 + d) * C + ci] = acc[d][i][j][r];
-        }
-  // bias partial: reduce the 16 pixel groups through LDS
-  float* red = reinterpret_cast<float*>(smem_raw);
-  __syncthreads();
-  red[dbg * C + dbc] = dbacc[0];
-  red[dbg * C + dbc + 1] = dbacc[1];
-  __syncthreads();
-  if (tid < C) {
-    float sum = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sum += red[q * C + tid];
-    dbpart[(long)blockIdx.x * C + tid] = sum;
-  }
-}
-
-// ------------------------------------------------------------------ 16-bit wgrad, v2 at C = 128
-// conv3x3_wgrad_v2_kernel's plan at the Swin-B width.  All nine taps of 128 x 128 are 576 KB of
-// f32 accumulators, more than a CU's register file, so a workgroup owns one HALF of the output
-// channels: block 2 s + h takes the tiles of pixel share s (s, s + nshare, ...) and co
-// 64 h .. 64 h + 63.  Same 12 waves (dy x co half of the block's 64 x ci half), each 3 dx x
-// 2 co tiles x 4 ci tiles = 96 accumulator registers; the X halo [6 x 34][128] sits at a pixel
-// stride of 136 elements (17 slots), the block's dY half-tile [128][64] at 72 (9 slots): pixels
-// two apart are 136 / 72 dwords = 8 mod 64 banks apart in both images, i.e. the 8 pixels of one
-// parity that a half-wave's k-strided read touches sit on distinct 32-B bank spans, as at 96.
-// Each X band is staged by the two blocks of a share.  Partials: chunk s of [chunk][dy][co][dx][ci] + db[chunk][co], each block
-// writing its 64 co rows -- the layout and the deterministic reduction are unchanged, over
-// nshare chunks.
-template <typename T, bool IN_D2S, bool IN_GELU>
-__global__ void __launch_bounds__(768) conv3x3_wgrad_v2h_kernel(const bf16_t* __restrict__ X,
-                                                                const bf16_t* __restrict__ DY,
-                                                                float* __restrict__ part,
-                                                                float* __restrict__ dbpart, ConvGeom g,
-                                                                int ntiles) {
-  constexpr int C = 128, COB = 64, TH = 4, TWV = 32, NW = 12;
-  constexpr int NI = COB / 32, NJ = C / 32;  // 16-wide co / ci tiles per wave
-  constexpr int PSX = C + 8, SLX = PSX / 8;  // X image: pixel stride, 16-B slots per pixel (16 + 1 pad)
-  constexpr int PSD = COB + 8, SLD = PSD / 8;  // dY image (8 + 1 pad)
-  constexpr int HWD = TWV + 2;
-  constexpr int HPIX = (TH + 2) * HWD;       // 204 halo pixels
-  constexpr int DPIX = TH * TWV;             // 128 dY pixels
-  constexpr int XSLOT = HPIX * SLX;          // slots of the X image; the dY image follows
-  constexpr int NSLOT = XSLOT + DPIX * SLD;
-  constexpr int NINS = (NSLOT + 63) / 64;    // DMA wave-instructions per tile
-  constexpr int PER_WAVE = (NINS + NW - 1) / NW;
-  constexpr int BUF = NINS * 64 * 8;         // elements per LDS buffer (covers the overrun)
-  static_assert(2 * BUF * sizeof(bf16_t) <= 160 * 1024, "LDS");
-  static_assert(2 * ((3 * HWD + 2) * PSX + 16 * (NJ - 1) + 32 * PSX) < 65536, "fragment read offsets are immediates");
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef __attribute__((address_space(1))) void glb_void;
-
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  bf16_t* lds = reinterpret_cast<bf16_t*>(smem_raw);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int dy = wave >> 2, coh = (wave >> 1) & 1, cih = wave & 1;
-  const int share = blockIdx.x >> 1, half = blockIdx.x & 1, nshare = gridDim.x >> 1;
-  const int tiles_x = (g.W + TWV - 1) / TWV, tiles_y = (g.H + TH - 1) / TH;
-  const int per_img = tiles_x * tiles_y;
-
-  auto coords = [&](int tile, int& b, int& y0, int& x0) {
-    b = tile / per_img;
-    const int r = tile - b * per_img;
-    y0 = (r / tiles_x) * TH;
-    x0 = (r - (r / tiles_x) * tiles_x) * TWV;
-  };
-  // issue this wave's DMAs of tile `tile` into buffer `buf`
-  auto stage = [&](int tile, int buf) __attribute__((always_inline)) {
-    int b, y0, x0;
-    coords(tile, b, y0, x0);
-    const int ln = opaque(lane);
-#pragma unroll
-    for (int r = 0; r < PER_WAVE; ++r) {
-      const int k = wave + NW * r;
-      if (k < NINS) {
-        const int s = 64 * k + ln;
-        const void* src = zero_src(s);
-        if (s < XSLOT) {
-          const int pix = s / SLX, ch0 = s - (s / SLX) * SLX;
-          const int ch = ch0 < SLX - 1 ? ch0 : 0;  // pad slot: re-read chunk 0 of the pixel
-          const int row = pix / HWD, col = pix - (pix / HWD) * HWD;
-          const int y = y0 - 1 + row, x = x0 - 1 + col;
-          if (y >= 0 && y < g.H && x >= 0 && x < g.W) src = X + pix_off32<IN_D2S>(b, y, x, g.H, g.W, C) + ch * 8;
-        } else if (s < NSLOT) {
-          const int t = s - XSLOT;
-          const int dp = t / SLD, ch0 = t - (t / SLD) * SLD;
-          const int ch = ch0 < SLD - 1 ? ch0 : 0;
-          const int y = y0 + dp / TWV, x = x0 + dp % TWV;
-          if (y < g.H && x < g.W) src = DY + pix_off32<false>(b, y, x, g.H, g.W, C) + COB * half + ch * 8;
-        }
-        __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(lds + buf * BUF + 64 * 8 * k), 16, 0, 0);
       }
     }
   };
@@ -1565,8 +1396,8 @@ __global__ void __launch_bounds__(768) conv3x3_wgrad_v2h_kernel(const bf16_t* __
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc[d][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   float dbacc[2] = {0.f, 0.f};
-  // bias gradient: threads 0 .. 511 = 16 pixel groups x 32 channel pairs
-  const bool dbon = tid < 16 * (COB / 2);
+  // bias gradient: 16 pixel groups x COB / 2 channel pairs (all 768 threads at 96, 512 at 128)
+  const bool dbon = 16 * (COB / 2) >= 64 * NW || tid < 16 * (COB / 2);
   const int dbc = 2 * (tid % (COB / 2)), dbg = dbon ? tid / (COB / 2) : 0;
 
   int tile = share;
@@ -1584,7 +1415,8 @@ __global__ void __launch_bounds__(768) conv3x3_wgrad_v2h_kernel(const bf16_t* __
     const bf16_t* sD = sX + HPIX * PSX;
     // All LDS reads of the tile are untracked (inline asm): a compiler-visible ds_read would
     // be preceded by vmcnt(0) for the next tile's pending LDS-DMA and serialise the two.
-    {
+    // bias gradient: 8 pixels per group and tile (ablation 65536: none)
+    if constexpr (!(MSU_EXP & 65536)) {
       const uint32_t ba = lds_u32(sD + dbg * PSD + dbc);
       uint32_t v[DPIX / 16];
       unroll_for<DPIX / 16>([&](auto P) {
@@ -1598,35 +1430,49 @@ __global__ void __launch_bounds__(768) conv3x3_wgrad_v2h_kernel(const bf16_t* __
         dbacc[1] += Fmt16<T>::hi(v[p]);
       }
     }
-    // lane part of a k-strided fragment read (as conv3x3_wgrad_v2_kernel): pixels
-    // 2(4g + q) + half-wave, columns 4(lane&3); everything else is an immediate offset
+    // lane part of a k-strided fragment read: pixels 2(4g + q) + half (+16 for the second
+    // half of the fragment), g = lane group within the 32-lane half, q = (lane&15)>>2,
+    // columns 4(lane&3); everything else is an immediate offset.  Same pixel order for both
+    // operands; pixels of one parity sit on distinct 32-B bank spans (WG2), so each half's 32
+    // lanes hit all 64 banks once (pixels 8(lane>>4) + q: 2-way conflicts).
     const int lpix = 2 * (4 * ((lane >> 4) & 1) + ((lane & 15) >> 2)) + (lane >> 5);
-    const int lx = opaque(lpix * PSX + 4 * (lane & 3)), ld = opaque(lpix * PSD + 4 * (lane & 3));
+    const int lx = opaque(lpix * PSX + 4 * (lane & 3));
+    const int ld = PSD == PSX ? lx : opaque(lpix * PSD + 4 * (lane & 3));
     const uint32_t xa = lds_u32(sX + lx + dy * HWD * PSX + (C / 2) * cih);
     const uint32_t da = lds_u32(sD + ld + (COB / 2) * coh);
     unroll_for<TH>([&](auto R) {
       constexpr int r = decltype(R)::value;
-      // the dY fragments of row r serve all three dx
+      // the dY fragments of row r serve all three dx (read once per row, not once per dx: at 96
+      // 12 instead of 18 fragment reads per 27 MFMAs -- the LDS reads bound this loop).
+      // (Reading group g + 1's X fragments before group g's MFMAs measured no faster, r06x:
+      // the loop is bound by its operand traffic, ablations r06w.)
       bf16x8 af[NI];
       unroll_for<NI>([&](auto I) {
         constexpr int o = 2 * (r * TWV * PSD + 16 * decltype(I)::value);
-        af[decltype(I)::value] = tr8_untracked<o, o + 32 * PSD>(da);
+        if constexpr (MSU_EXP & 32768) af[decltype(I)::value] = bf16x8{};  // ablation: no fragment reads
+        else af[decltype(I)::value] = tr8_untracked<o, o + 32 * PSD>(da);
       });
       unroll_for<3>([&](auto D) {
         constexpr int d = decltype(D)::value;
         bf16x8 bf[NJ];
         unroll_for<NJ>([&](auto J) {
           constexpr int o = 2 * ((r * HWD + d) * PSX + 16 * decltype(J)::value);
-          bf[decltype(J)::value] = tr8_untracked<o, o + 32 * PSX>(xa);
+          if constexpr (MSU_EXP & 32768) bf[decltype(J)::value] = bf16x8{};
+          else bf[decltype(J)::value] = tr8_untracked<o, o + 32 * PSX>(xa);
         });
-        if constexpr (d == 0)
-          lds_wait_tie<0>(bf[0], bf[1], bf[2], bf[3], af[0], af[1]);
-        else
-          lds_wait_tie<0>(bf[0], bf[1], bf[2], bf[3]);
+        lds_wait_tie<0>();
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) vreg_pin(bf[j]);
+        if constexpr (d == 0) {
+#pragma unroll
+          for (int i = 0; i < NI; ++i) vreg_pin(af[i]);
+        }
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[d][i][j] = Fmt16<T>::mma16(af[i], bf[j], acc[d][i][j]);
+          for (int j = 0; j < NJ; ++j)
+            if constexpr (MSU_EXP & 16384) asm volatile("" ::"v"(af[i]), "v"(bf[j]));  // ablation: no MFMA
+            else acc[d][i][j] = Fmt16<T>::mma16(af[i], bf[j], acc[d][i][j]);
         __builtin_amdgcn_sched_barrier(0);
       });
     });
@@ -1849,44 +1695,25 @@ int launch_wgrad_nti(const ConvGeom& g, const T* X, const T* DY, float* part, fl
   return -2;
 }
 
-template <typename T, bool IN_D2S, bool IN_GELU>
+// Blocks SPLIT s + h = (pixel share s, co part h); nchunk / SPLIT shares, so the grid stays nchunk
+// workgroups.  Returns the number of partial chunks written (> 0) or an error (< 0).
+template <typename T, int C, bool IN_D2S, bool IN_GELU>
 int launch_wgrad_v2(const ConvGeom& g, const bf16_t* X, const bf16_t* DY, float* part, float* dbpart,
-                    int nblocks, hipStream_t st) {
-  constexpr int nins = ((6 * 34 + 4 * 32) * 13 + 63) / 64;
-  constexpr size_t lds = 2 * sizeof(bf16_t) * (size_t)nins * 64 * 8;
-  static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv3x3_wgrad_v2_kernel<T, IN_D2S, IN_GELU>;
+                    int nchunk, hipStream_t st) {
+  using G = WG2<C>;
+  // 32-bit element offsets inside the kernel (checked before any HIP call)
+  if ((long)g.B * g.H * g.W * C >= (1L << 31)) return -2;
+  auto kern = conv3x3_wgrad_v2_kernel<T, C, IN_D2S, IN_GELU>;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     attr_set = true;
   }
-  if ((long)g.B * g.H * g.W * 96 >= (1L << 31)) return -2;
-  const long ntiles = (long)g.B * ((g.W + 31) / 32) * ((g.H + 3) / 4);
-  // every block writes its partial slabs, even with no tile (zeros)
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(768), lds, st, X, DY, part, dbpart, g, (int)ntiles);
-  return MSU_CHECK_LAUNCH();
-}
-
-// C = 128: blocks 2 s + h = (pixel share s, co half h); nchunk / 2 shares, so the grid stays
-// nchunk workgroups.  Returns the number of partial chunks written (> 0) or an error (< 0).
-template <typename T, bool IN_D2S, bool IN_GELU>
-int launch_wgrad_v2h(const ConvGeom& g, const bf16_t* X, const bf16_t* DY, float* part, float* dbpart,
-                     int nchunk, hipStream_t st) {
-  constexpr int nslot = 6 * 34 * 17 + 4 * 32 * 9, nins = (nslot + 63) / 64;
-  constexpr size_t lds = 2 * sizeof(bf16_t) * (size_t)nins * 64 * 8;
-  static_assert(lds <= 160 * 1024, "LDS");
-  if ((long)g.B * g.H * g.W * 128 >= (1L << 31)) return -2;
-  auto kern = conv3x3_wgrad_v2h_kernel<T, IN_D2S, IN_GELU>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  const int nshare = nchunk >= 2 ? nchunk / 2 : 1;
-  const long ntiles = (long)g.B * ((g.W + 31) / 32) * ((g.H + 3) / 4);
+  const int nshare = nchunk >= G::SPLIT ? nchunk / G::SPLIT : 1;
+  const long ntiles = (long)g.B * ((g.W + G::TWV - 1) / G::TWV) * ((g.H + G::TH - 1) / G::TH);
   // every block writes its partial rows, even with no tile (zeros)
-  hipLaunchKernelGGL(kern, dim3((unsigned)(2 * nshare)), dim3(768), lds, st, X, DY, part, dbpart, g, (int)ntiles);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(G::SPLIT * nshare)), dim3(64 * G::NW), G::LDS, st, X, DY, part, dbpart, g,
+                     (int)ntiles);
   return MSU_CHECK_LAUNCH() ? -1 : nshare;
 }
 

@@ -1,6 +1,19 @@
 // Refine-conv weight-gradient entry points (kernels: conv3x3.h).
 #include "conv3x3.h"
 
+namespace {
+// in_mode bit 1 (d2s input) and bit 0 (GELU on load) as compile-time booleans: f(d2s, gelu)
+template <typename F>
+int with_in_mode(int in_mode, F f) {
+  switch (in_mode & 3) {
+    case 0: return f(std::false_type{}, std::false_type{});
+    case 1: return f(std::false_type{}, std::true_type{});
+    case 2: return f(std::true_type{}, std::false_type{});
+  }
+  return f(std::true_type{}, std::true_type{});
+}
+}  // namespace
+
 extern "C" {
 
 long msu_conv3x3_wgrad_workspace(int nchunk, int Cin, int Cout, int dtype, int unused) {
@@ -22,44 +35,26 @@ int msu_conv3x3_wgrad2(int dtype, int in_mode, const void* X, const void* dY, fl
   float* dbpart = workspace + (long)nchunk * 3 * Cout * 3 * g.CinP;
   int rc = -3;
   int nsum = nchunk;  // partial chunks to sum
-#define MSU_WG(T, D2S, GL) rc = wgrad_nt<T, D2S, GL>(g, X, dY, part, dbpart, nchunk, st)
-  if (msu_is16(dtype) && Cin == 96 && Cout == 96) {
+  // the widths with a persistent kernel (conv3x3_wgrad_v2_kernel); at 128 one co half per
+  // workgroup, so nchunk / 2 partial chunks
+  const bool v2 = msu_is16(dtype) && Cin == Cout && (Cin == 96 || (Cin == 128 && !conv3x3_generic_wide()));
+  if (v2) {
     const bf16_t* x = (const bf16_t*)X; const bf16_t* d = (const bf16_t*)dY;
-    MSU_DISPATCH16(dtype, T,
-      switch (in_mode & 3) {
-        case 0: rc = launch_wgrad_v2<T, false, false>(g, x, d, part, dbpart, nchunk, st); break;
-        case 1: rc = launch_wgrad_v2<T, false, true>(g, x, d, part, dbpart, nchunk, st); break;
-        case 2: rc = launch_wgrad_v2<T, true, false>(g, x, d, part, dbpart, nchunk, st); break;
-        case 3: rc = launch_wgrad_v2<T, true, true>(g, x, d, part, dbpart, nchunk, st); break;
-      });
-  } else if (msu_is16(dtype) && Cin == 128 && Cout == 128 && !conv3x3_generic_wide()) {
-    // one co half per workgroup: nchunk / 2 pixel shares (conv3x3_wgrad_v2h_kernel)
-    const bf16_t* x = (const bf16_t*)X; const bf16_t* d = (const bf16_t*)dY;
-    MSU_DISPATCH16(dtype, T,
-      switch (in_mode & 3) {
-        case 0: rc = launch_wgrad_v2h<T, false, false>(g, x, d, part, dbpart, nchunk, st); break;
-        case 1: rc = launch_wgrad_v2h<T, false, true>(g, x, d, part, dbpart, nchunk, st); break;
-        case 2: rc = launch_wgrad_v2h<T, true, false>(g, x, d, part, dbpart, nchunk, st); break;
-        case 3: rc = launch_wgrad_v2h<T, true, true>(g, x, d, part, dbpart, nchunk, st); break;
-      });
+    MSU_DISPATCH16(dtype, T, rc = with_in_mode(in_mode, [&](auto D2S, auto GL) {
+      constexpr bool d2s = decltype(D2S)::value, gl = decltype(GL)::value;
+      return Cin == 96 ? launch_wgrad_v2<T, 96, d2s, gl>(g, x, d, part, dbpart, nchunk, st)
+                       : launch_wgrad_v2<T, 128, d2s, gl>(g, x, d, part, dbpart, nchunk, st);
+    }));
     if (rc > 0) { nsum = rc; rc = 0; }
   } else if (msu_is16(dtype)) {
-    MSU_DISPATCH16(dtype, T,
-      switch (in_mode & 3) {
-        case 0: MSU_WG(T, false, false); break;
-        case 1: MSU_WG(T, false, true); break;
-        case 2: MSU_WG(T, true, false); break;
-        case 3: MSU_WG(T, true, true); break;
-      });
+    MSU_DISPATCH16(dtype, T, rc = with_in_mode(in_mode, [&](auto D2S, auto GL) {
+      return wgrad_nt<T, decltype(D2S)::value, decltype(GL)::value>(g, X, dY, part, dbpart, nchunk, st);
+    }));
   } else {
-    switch (in_mode & 3) {
-      case 0: MSU_WG(float, false, false); break;
-      case 1: MSU_WG(float, false, true); break;
-      case 2: MSU_WG(float, true, false); break;
-      case 3: MSU_WG(float, true, true); break;
-    }
+    rc = with_in_mode(in_mode, [&](auto D2S, auto GL) {
+      return wgrad_nt<float, decltype(D2S)::value, decltype(GL)::value>(g, X, dY, part, dbpart, nchunk, st);
+    });
   }
-#undef MSU_WG
   if (rc) return rc;
   // deterministic chunk sums (one launch for the weight slab and the bias), then the
   // [dy][co][dx][ci] -> [co][ci][dy][dx] permutation

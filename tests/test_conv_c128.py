@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = "/opt/rocm/llvm/bin/llvm-readelf"
 F32, BF16, F16 = 0, 1, 2
 
-# the weight gradient at 128 ships too (conv3x3_wgrad_v2h_kernel): bit 1 is set
+# the weight gradient at 128 ships too (conv3x3_wgrad_v2_kernel at C = 128): bit 1 is set
 WGRAD_128 = True
 
 # launch forms routed to the persistent kernel, as template flags
@@ -138,12 +138,20 @@ def test_only_the_two_widths_are_built(v3_meta):
             assert any(f"conv3x3_v3_kernelI{fmt}{flags}Li96ELi32EEE" in k for k in v3_meta), (fmt, form)
 
 
+@pytest.fixture(scope="module")
+def wgrad_meta():
+    return {k: v for k, v in _kernel_metadata(_lib.LIB_PATH).items() if "wgrad_v2" in k}
+
+
 @pytest.mark.parametrize("fmt", ["t", "DF16_"], ids=["bf16", "f16"])
 @pytest.mark.parametrize("d2s,gelu", [(0, 0), (0, 1), (1, 0), (1, 1)])
-def test_c128_wgrad_instantiations_without_scratch(fmt, d2s, gelu):
-    meta = {k: v for k, v in _kernel_metadata(_lib.LIB_PATH).items() if "conv3x3_wgrad_v2h_kernel" in k}
-    assert len(meta) == 8, sorted(meta)
-    hits = [k for k in meta if f"conv3x3_wgrad_v2h_kernelI{fmt}Lb{d2s}ELb{gelu}EEE" in k]
+@pytest.mark.parametrize("C", [96, 128])
+def test_c128_wgrad_instantiations_without_scratch(wgrad_meta, C, fmt, d2s, gelu):
+    """One persistent weight-gradient kernel, 2 formats x 4 input modes x 2 widths."""
+    assert not [k for k in wgrad_meta if "wgrad_v2h" in k], "the C = 128 copy of the kernel is gone"
+    meta = {k: v for k, v in wgrad_meta.items() if "conv3x3_wgrad_v2_kernel" in k}
+    assert len(meta) == 16, sorted(meta)
+    hits = [k for k in meta if f"conv3x3_wgrad_v2_kernelI{fmt}Li{C}ELb{d2s}ELb{gelu}EEE" in k]
     assert len(hits) == 1, sorted(meta)
     m = meta[hits[0]]
     assert m["private_segment_fixed_size"] == 0, m
