@@ -14,6 +14,9 @@
 * ``conv3x3_ref``: ``conv2d(a, W, b, padding=1)`` on NHWC tensors as nine shifted fp32
   matmuls (autograd gives dA, dW, db), so the 1024^2 references need neither the CPU nor a
   library convolution.
+* ``conv3x3_ref64`` / ``conv3x3_abs64`` / ``conv3x3_wgrad_ref64`` / ``conv3x3_wgrad_abs64`` /
+  ``gelu64`` / ``gelu_grad64``: the refine-conv family in float64 with its condition terms
+  (tests/test_gpu_conv_matrix.py judges every kernel of csrc/conv3x3.h against them).
 * ``ln_plain_ref`` / ``ln_add_ref`` / ``ln_merge_ref`` / ``ln_d2s2_ref`` / ``ln_head_ref``: the
   four input modes of csrc/layernorm.hip and its 1-channel head in float64 (the one exception to
   "fp32" above: tests/test_gpu_ln_matrix.py judges f32 kernels against them).
@@ -100,6 +103,77 @@ def d2s4(x, C):
     """FinalPatchExpand_X4_V2's rearrange 'b h w (p1 p2 c) -> b (h p1) (w p2) c' (p = 4)."""
     B, h, w, _ = x.shape
     return x.view(B, h, w, 4, 4, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 4 * h, 4 * w, C)
+
+
+# ----------------------------------------------------------------------------- refine-conv family
+# fp64 references of csrc/conv3x3.h (tests/test_gpu_conv_matrix.py), evaluated on the operands'
+# device and fed exactly the stored operands.  No library convolution: nine shifted, zero-padded
+# slices, one torch.matmul each.
+def d2s4_rearrange(x, C):
+    """The pre-depth-to-space tensor [B, H/4, W/4, 16 C] as the image [B, H, W, C], through the
+    rearrange the conv tests use."""
+    from einops import rearrange
+    return rearrange(x, "b h w (p1 p2 c) -> b (h p1) (w p2) c", p1=4, p2=4, c=C)
+
+
+def gelu64(x):
+    x = x.double()
+    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def gelu_grad64(x):
+    x = x.double()
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+def _shifted(a):
+    """The nine zero-padded shifts of a [B, H, W, C]: ((dy, dx), a[:, y + dy - 1, x + dx - 1, :])."""
+    B, H, W, _ = a.shape
+    ap = F.pad(a, (0, 0, 1, 1, 1, 1))
+    for dy in range(3):
+        for dx in range(3):
+            yield (dy, dx), ap[:, dy:dy + H, dx:dx + W, :]
+
+
+def conv3x3_ref64(a, w, b=None, d2s=False):
+    """conv2d(a, w, b, padding=1) in float64.  a: [B, H, W, Cin] (d2s: the pre-depth-to-space
+    [B, H/4, W/4, 16 Cin]), w: [Cout, Cin, 3, 3], b: [Cout] or None -> [B, H, W, Cout]."""
+    w = w.double()
+    a = a.double()
+    if d2s:
+        a = d2s4_rearrange(a, w.shape[1])
+    z = torch.zeros(a.shape[:3] + (w.shape[0],), dtype=torch.float64, device=a.device)
+    for (dy, dx), s in _shifted(a):
+        z += torch.matmul(s, w[:, :, dy, dx].t())
+    return z if b is None else z + b.double()
+
+
+def conv3x3_abs64(a, w, b=None, d2s=False):
+    """The same sum over absolute values: the condition term A = sum |a| |w| + |b| of every output."""
+    return conv3x3_ref64(a.double().abs(), w.double().abs(), None if b is None else b.double().abs(), d2s)
+
+
+def conv3x3_dgrad_weight(w):
+    """The weight whose conv3x3 of dz is the input gradient: [Cin, Cout, 3, 3], taps flipped."""
+    return w.flip(2, 3).transpose(0, 1).contiguous()
+
+
+def conv3x3_wgrad_ref64(a, dz, dtype=torch.float64):
+    """(dW [Cout, Cin, 3, 3], db [Cout]) of z = conv3x3(a, W) + b: the nine a_shifted^T @ dz
+    products over all pixels.  a: the conv's input image [B, H, W, Cin] (already float64), dz:
+    [B, H, W, Cout].  dtype = float32 evaluates the same products with the float64 operands cast
+    to f32 (the figure the sum tolerance of the conv matrix is derived from)."""
+    Cin, Cout = a.shape[-1], dz.shape[-1]
+    d = dz.double().to(dtype).reshape(-1, Cout)
+    dw = torch.empty(Cout, Cin, 3, 3, dtype=dtype, device=a.device)
+    for (dy, dx), s in _shifted(a.double().to(dtype)):
+        dw[:, :, dy, dx] = torch.matmul(s.reshape(-1, Cin).t(), d).t()
+    return dw, d.sum(0)
+
+
+def conv3x3_wgrad_abs64(a, dz):
+    """sum_pixels |a| |dz| per weight element and sum_pixels |dz| per bias element."""
+    return conv3x3_wgrad_ref64(a.double().abs(), dz.double().abs())
 
 
 # ----------------------------------------------------------------------------- LayerNorm family
