@@ -4,13 +4,17 @@
 // around them:
 //   * depth-to-space 4x4 of the expand output (model_parts.py:464-465) is folded into the
 //     input addressing (IN_D2S) -- the d2s tensor and the NHWC->NCHW permute never exist;
-//   * GELU of the conv input (model_parts.py:460, :469) is applied on load (IN_GELU), so
-//     only pre-activations are stored;
+//   * GELU of the conv input (model_parts.py:460, :469) comes from the producer: its epilogue
+//     stores GELU(Y) beside the pre-activation Y (DUAL), and the conv loads that activation as
+//     it is (ops.refine_conv_act, the model's path).  GELU on load (IN_GELU, ops.refine_conv)
+//     is kept for tests and tools: the generic kernel and the weight gradients have it;
 //   * bias add in the epilogue; backward-data multiplies by GELU'(pre-activation) in the
 //     epilogue and scatters through the same d2s map (OUT_D2S / OUT_GGRAD).
 // fwd and dgrad share one kernel (dgrad = conv with spatially flipped, ci<->co swapped
-// weights).  wgrad reads both operands k-strided from natural [pixel][channel] LDS images
-// with ds_read_b64_tr_b16 (bf16) and writes deterministic per-block partials.
+// weights): conv3x3_kernel for any width and dtype, conv3x3_v3_kernel (persistent, LDS-DMA)
+// for 16-bit C = 96 and 128 without GELU on load; persistent_width() picks.  wgrad reads both
+// operands k-strided from natural [pixel][channel] LDS images with ds_read_b64_tr_b16 (bf16)
+// and writes deterministic per-block partials.
 #pragma once
 #include <cstdlib>
 #include <utility>
@@ -19,8 +23,13 @@
 #include "mfma_frag.h"
 #include "reduce.h"
 
-// msu_conv_mode bit 1 (conv3x3.hip), read by the weight-gradient dispatch as well
-int conv3x3_generic_wide();
+// msu_conv_mode (defined in conv3x3.hip, one copy for both translation units).
+// bit 0 (default on; A/B switch MSU_CONV_DYN): conv3x3_v3_kernel takes tiles from the
+// per-stream queue slot instead of the static blockIdx.x + k * gridDim.x schedule
+extern int g_conv_dyn;
+// bit 1 (default off; the A/B handle of tools and tests, no environment switch): widths other
+// than 96 take the generic kernels
+extern int g_conv_generic_wide;
 
 // MSU_EXP: ablation bits for timing experiments only (tools/build_exp.sh); 0 in every real build
 #ifndef MSU_EXP
@@ -231,22 +240,10 @@ __global__ void __launch_bounds__(64 * (TH / MT)) conv3x3_kernel(const T* __rest
   }
 }
 
-// ------------------------------------------------------------------ 16-bit fwd / dgrad, v2
-// Persistent implicit GEMM on v_mfma_f32_32x32x16_{bf16,f16} (raw 16-bit storage; T = format) (Cout = 32*NCT, CinP = 16*KS).  One
-// workgroup of NW waves per CU loops over output tiles of NW*MT rows x 32 pixels x all
-// Cout; wave w owns MT image rows.  D[co][pixel] = W_tap[co][ci] * X[ci][pixel]: the weight
-// fragment is the A operand, so each lane ends with 4 consecutive output channels of one
-// pixel (8-B stores).  Everything is register staged:
-//   * weights: a ring of three register sets; W(tap+1) is written to the other LDS buffer
-//     while tap runs (WDB: one barrier per tap; else between two barriers after the tap),
-//     its global load issued three taps earlier;
-//   * halo of the next tile: loaded after tap 0, GELU-converted in registers a third per
-//     tap (waves of the lower half at taps 2-4, the upper half at 5-7: on each SIMD one wave
-//     converts while its partner issues MFMAs), stored to LDS after tap 8;
-//   * dgrad: the pre-activation S of the tile's outputs is prefetched at tap 5 for the
-//     GELU' epilogue.
-// Index math of the halo chunks goes through opaque() so it is recomputed per tile instead
-// of pinning registers for the whole persistent loop.
+// ------------------------------------------------------------------ 16-bit helpers
+// Shared by the persistent kernels below (conv3x3_v3_kernel, conv3x3_wgrad_v2_kernel): eight
+// 16-bit values of a 16-B chunk as floats, GELU of a chunk in registers (the DUAL epilogue, the
+// weight gradient's in-place conversion), and a compile-time loop over integral constants.
 template <typename T> MSU_DEV void unpack8(const u32x4& q, float (&v)[8]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -267,255 +264,14 @@ MSU_DEV void static_for(F&& f, std::integer_sequence<int, Is...>) {
   (f(IC<Is>{}), ...);
 }
 
-template <typename T, int NCT, int KS, int NW, int MT, bool WDB, bool IN_D2S, bool IN_GELU, bool OUT_D2S,
-          bool OUT_GGRAD, bool BIAS, bool DUAL>
-__global__ void __launch_bounds__(64 * NW) conv3x3_v2_kernel(const bf16_t* __restrict__ X,
-                                                         const bf16_t* __restrict__ Wt,
-                                                         const float* __restrict__ bias,
-                                                         const bf16_t* __restrict__ S,
-                                                         bf16_t* __restrict__ Y, bf16_t* __restrict__ Y2,
-                                                         ConvGeom g, int ntiles) {
-  constexpr int TH = NW * MT, TWV = 32;
-  constexpr int CinP = KS * 16, Cout = NCT * 32;
-  constexpr int PS = CinP + 8;           // LDS pixel / weight-row stride: conflict-free b128 reads
-  constexpr int CPP = CinP / 8;          // 16-B chunks per pixel
-  constexpr int HWD = TWV + 2;           // halo width
-  constexpr int HPIX = (TH + 2) * HWD;
-  constexpr int HCH = HPIX * CPP;
-  constexpr int NTHR = 64 * NW;
-  constexpr int NHC = (HCH + NTHR - 1) / NTHR;
-  constexpr int WCH = Cout * CPP;
-  constexpr int NWC = (WCH + NTHR - 1) / NTHR;
-  constexpr int WIMG = Cout * PS;        // elements of one LDS weight image
-
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  bf16_t* sX = reinterpret_cast<bf16_t*>(smem_raw);
-  bf16_t* sW = sX + HPIX * PS;           // [WDB ? 2 : 1][Cout][PS]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_x = (g.W + TWV - 1) / TWV, tiles_y = (g.H + TH - 1) / TH;
-  const int per_img = tiles_x * tiles_y;
-
-  u32x4 hr[NHC];
-  u32x4 w0[NWC], w1[NWC], w2[NWC];       // weight register ring (sets picked at compile time)
-  u32x4 sp[OUT_GGRAD ? MT : 1][OUT_GGRAD ? NCT : 1][2];
-
-  auto coords = [&](int tile, int& b, int& y0, int& x0) {
-    b = tile / per_img;
-    const int r = tile - b * per_img;
-    y0 = (r / tiles_x) * TH;
-    x0 = (r - (r / tiles_x) * tiles_x) * TWV;
-  };
-  // branch-free halo load: out-of-image / padding chunks load a clamped in-image address and
-  // are zeroed by a select
-  auto load_halo = [&](int tile) {
-    int b, y0, x0;
-    coords(tile, b, y0, x0);
-    const int t = opaque(tid);
-#pragma unroll
-    for (int c = 0; c < NHC; ++c) {
-      const int i = t + NTHR * c;
-      const int pix = i / CPP, ch = i - (i / CPP) * CPP;
-      const int row = pix / HWD, col = pix - (pix / HWD) * HWD;
-      const int y = y0 - 1 + row, x = x0 - 1 + col;
-      const bool ok = i < HCH && y >= 0 && y < g.H && x >= 0 && x < g.W && ch * 8 < g.Cin;
-      const int yc = min(max(y, 0), g.H - 1), xc = min(max(x, 0), g.W - 1);
-      const int chc = ch * 8 < g.Cin ? ch : 0;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(X + pix_off32<IN_D2S>(b, yc, xc, g.H, g.W, g.Cin) + chc * 8);
-      hr[c] = ok ? v : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  auto store_halo = [&]() {
-    const int t = opaque(tid);
-#pragma unroll
-    for (int c = 0; c < NHC; ++c) {
-      const int i = t + NTHR * c;
-      if (HCH % NTHR == 0 || c + 1 < NHC || i < HCH) {
-        const int pix = i / CPP, ch = i - (i / CPP) * CPP;
-        *reinterpret_cast<u32x4*>(sX + pix * PS + ch * 8) = hr[c];
-      }
-    }
-  };
-  auto load_w = [&](int tap, u32x4 (&dst)[NWC]) {
-    const bf16_t* src = Wt + (long)tap * Cout * CinP;
-#pragma unroll
-    for (int c = 0; c < NWC; ++c) {
-      const int i = min(tid + NTHR * c, WCH - 1);
-      dst[c] = *reinterpret_cast<const u32x4*>(src + (long)i * 8);
-    }
-  };
-  auto store_w = [&](const u32x4 (&srcr)[NWC], bf16_t* dst) {
-#pragma unroll
-    for (int c = 0; c < NWC; ++c) {
-      const int i = tid + NTHR * c;
-      if (WCH % NTHR == 0 || c + 1 < NWC || i < WCH) {
-        const int co = i / CPP, ch = i - (i / CPP) * CPP;
-        *reinterpret_cast<u32x4*>(dst + co * PS + ch * 8) = srcr[c];
-      }
-    }
-  };
-  // ring step: write set K to LDS, refill it with W(tap); sets are named, never selected
-  // through a reference, so they stay in registers
-  auto ring = [&](auto K, bf16_t* dst, int tap) {
-    if constexpr (decltype(K)::value == 0) { store_w(w0, dst); load_w(tap, w0); }
-    else if constexpr (decltype(K)::value == 1) { store_w(w1, dst); load_w(tap, w1); }
-    else { store_w(w2, dst); load_w(tap, w2); }
-  };
-  auto out_off = [&](int b, int y, int x, int co) -> int { return pix_off32<OUT_D2S>(b, y, x, g.H, g.W, Cout) + co; };
-
-  int tile = blockIdx.x;
-  if (tile >= ntiles) return;
-  // prologue: halo of the first tile, W(0) in LDS buffer 0, W(1..3) in flight in sets 1, 2, 0
-  load_halo(tile);
-  if constexpr (IN_GELU && !(MSU_EXP & 2)) {
-#pragma unroll
-    for (int c = 0; c < NHC; ++c) hr[c] = gelu8<T>(hr[c]);
-  }
-  store_halo();
-  load_w(0, w0);
-  store_w(w0, sW);
-  load_w(1, w1);
-  load_w(2, w2);
-  load_w(3, w0);
-  __syncthreads();
-
-  const int xl = lane & 31, kh = 8 * (lane >> 5);
-  int wbuf = 0;
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int next = tile + gridDim.x;
-    int b, y0, x0;
-    coords(tile, b, y0, x0);
-    const int xo = x0 + xl;
-    f32x16 acc[MT][NCT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int n = 0; n < NCT; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
-
-    static_for([&](auto TAP) {
-      constexpr int tap = decltype(TAP)::value;
-      constexpr int dy = tap / 3, dx = tap % 3;
-      const bf16_t* wcur = sW + (WDB ? wbuf * WIMG : 0);
-      if constexpr (WDB) {
-        // W(tap+1) into the other buffer (read during tap-1, released by its barrier)
-        if constexpr (!(MSU_EXP & 8)) ring(IC<(tap + 1) % 3>{}, sW + (wbuf ^ 1) * WIMG, (tap + 4) % 9);
-      }
-      if constexpr (tap == 0 && !(MSU_EXP & 4)) {
-        if (next < ntiles) load_halo(next);
-      }
-      if constexpr (IN_GELU && tap >= 2 && tap <= 7 && !(MSU_EXP & 2)) {
-        // GELU of the prefetched halo, a third per tap: waves 0..NW/2-1 at taps 2-4, the
-        // others at taps 5-7, so on every SIMD one wave converts while its partner runs MFMAs
-        constexpr int part = (tap - 2) % 3;
-        constexpr int c0 = part * ((NHC + 2) / 3);
-        constexpr int c1 = (c0 + (NHC + 2) / 3) < NHC ? (c0 + (NHC + 2) / 3) : NHC;
-        if ((wave < NW / 2) == (tap <= 4)) {
-#pragma unroll
-          for (int c = c0; c < c1; ++c) hr[c] = gelu8<T>(hr[c]);
-        }
-      }
-      if constexpr (OUT_GGRAD && tap == 5) {
-        if (xo < g.W) {
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            const int y = min(y0 + wave * MT + m, g.H - 1);
-#pragma unroll
-            for (int n = 0; n < NCT; ++n)
-#pragma unroll
-              for (int pp = 0; pp < 2; ++pp)
-                sp[m][n][pp] = *reinterpret_cast<const u32x4*>(S + out_off(b, y, xo, 32 * n + 16 * pp + 8 * (lane >> 5)));
-          }
-        }
-      }
-      // fragments double buffered in registers: the reads of k-step ks+1 are issued before
-      // the MFMAs of ks; a scheduling fence per k-step keeps the compiler from hoisting more
-      const bf16_t* xb = sX + ((wave * MT + dy) * HWD + dx + xl) * PS + kh;
-      const bf16_t* wb = wcur + xl * PS + kh;
-      bf16x8 xa[2][MT], wf[2][NCT];
-      auto read_frags = [&](int ks, int set) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m) xa[set][m] = *reinterpret_cast<const bf16x8*>(xb + m * HWD * PS + ks * 16);
-#pragma unroll
-        for (int n = 0; n < NCT; ++n) wf[set][n] = *reinterpret_cast<const bf16x8*>(wb + n * 32 * PS + ks * 16);
-      };
-      read_frags(0, 0);
-      static_for([&](auto KSI) {
-        constexpr int ks = decltype(KSI)::value;
-        constexpr int cur = ks & 1;
-        if constexpr (ks + 1 < KS) read_frags(ks + 1, cur ^ 1);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int n = 0; n < NCT; ++n)
-          {
-            if constexpr (MSU_EXP & 32)
-              acc[m][n][0] += (float)wf[cur][n][0] * (float)xa[cur][m][1];
-            else
-              acc[m][n] = Fmt16<T>::mma32(wf[cur][n], xa[cur][m], acc[m][n]);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      }, std::make_integer_sequence<int, KS>{});
-      if constexpr (!(MSU_EXP & 16) || tap == 8) __syncthreads();
-      if constexpr (!WDB) {
-        ring(IC<(tap + 1) % 3>{}, sW, (tap + 4) % 9);
-      }
-      if constexpr (tap == 8) {
-        if (next < ntiles) store_halo();
-      }
-      if constexpr (!WDB || tap == 8) __syncthreads();
-      if constexpr (WDB) wbuf ^= 1;
-    }, std::make_integer_sequence<int, 9>{});
-
-    // epilogue: lane holds pixel xo, channels 32n + 8q + 4(lane>>5) + e (q = 0..3) of its rows;
-    // v_permlane32_swap of groups q = 2pp and 2pp+1 gives lane l < 32 channels 32n + 16pp + 0..7
-    // and lane l + 32 channels 32n + 16pp + 8..15 of the same pixel: one 16-B store each
-    if (xo < g.W) {
-#pragma unroll
-      for (int n = 0; n < NCT; ++n)
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-          const int co = 32 * n + 16 * pp + 8 * (lane >> 5);
-          float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          if constexpr (BIAS) {
-            const float4 t0 = *reinterpret_cast<const float4*>(bias + co);
-            const float4 t1 = *reinterpret_cast<const float4*>(bias + co + 4);
-            bv[0] = t0.x; bv[1] = t0.y; bv[2] = t0.z; bv[3] = t0.w;
-            bv[4] = t1.x; bv[5] = t1.y; bv[6] = t1.z; bv[7] = t1.w;
-          }
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            const int y = y0 + wave * MT + m;
-            float v[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[m][n][8 * pp + i]),
-                                                              __float_as_uint(acc[m][n][8 * pp + 4 + i]), false, false);
-              v[i] = __uint_as_float(r[0]) + bv[i];
-              v[4 + i] = __uint_as_float(r[1]) + bv[4 + i];
-            }
-            if (y >= g.H) continue;
-            if constexpr (OUT_GGRAD) {
-              const u32x4 t = sp[m][n][pp];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                v[2 * i] *= gelu_grad_fast(Fmt16<T>::lo(t[i]));
-                v[2 * i + 1] *= gelu_grad_fast(Fmt16<T>::hi(t[i]));
-              }
-            }
-            const u32x4 pk = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
-            if (!(MSU_EXP & 1) || v[0] == 1.2345e-30f) *reinterpret_cast<u32x4*>(Y + out_off(b, y, xo, co)) = pk;
-            if constexpr (DUAL) *reinterpret_cast<u32x4*>(Y2 + out_off(b, y, xo, co)) = gelu8<T>(pk);
-          }
-        }
-    }
-  }
-}
-
 // ------------------------------------------------------------------ 16-bit fwd / dgrad, v3 (C = 96, 128)
-// The v2 kernel (8 waves x one output row) spends as many LDS cycles as MFMA cycles: per tap
-// and wave 24 ds_read_b128 for 18 MFMAs, plus 24 KB of register-staged weight writes per tap.
-// v3 halves both per output pixel:
+// Persistent implicit GEMM on v_mfma_f32_{32x32x16,16x16x32}_{bf16,f16} (raw 16-bit storage;
+// T = format): one workgroup of 8 waves per CU loops over output tiles, D[co][pixel] =
+// W_tap[co][ci] * X[ci][pixel] with the weight fragment as the A operand, so each lane ends
+// with consecutive output channels of one pixel.  The plain plan (8 waves x one output row,
+// padded LDS images, weights staged through registers) spends as many LDS cycles as MFMA
+// cycles: per tap and wave 24 ds_read_b128 for 18 MFMAs, plus 24 KB of weight ds_writes per
+// tap.  v3 halves both per output pixel:
 //   * a tile is 16 rows x 32 pixels x 96 channels; wave w owns rows 2w, 2w + 1, so each weight
 //     fragment feeds two MFMAs (reads per MFMA 5/6 instead of 4/3);
 //   * the halo [18][34][96] and the weight image of a tap [96][96] are stored UNPADDED with
@@ -525,8 +281,8 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_v2_kernel(const bf16_t* __res
 //     permuted by the same swizzle) into the other of two weight images while tap t runs --
 //     no registers and no ds_write for the weight ring, one barrier per tap;
 //   * the next tile's halo is loaded into registers at tap 1 and written to LDS after tap 8.
-// Epilogue as v2 (bias, DUAL = GELU(Y) as a second output, GELU'(S) for the backward-data
-// launches with S prefetched at tap 7, 16-B stores after a permlane32 swap).
+// Epilogue: bias, DUAL = GELU(Y) as a second output, GELU'(S) for the backward-data launches
+// with S prefetched at tap 7, 16-B stores after a permlane32 (16x16x32: permlane16) swap.
 //
 // C = 128 (Swin-B) is the same kernel at another width: every count below comes from V3W<C>.
 // Its 18 x 34 halo would be 157 KB, so a tile is 8 rows x 32 pixels (one row per wave; halo
@@ -1560,46 +1316,43 @@ int launch_conv(const ConvGeom& g, const T* X, const T* Wt, const float* bias, c
   return MSU_CHECK_LAUNCH();
 }
 
-// msu_conv_mode bit 0 (default on; A/B switch MSU_CONV_DYN): conv3x3_v3_kernel takes tiles
-// from the per-stream queue slot instead of the static blockIdx.x + k * gridDim.x schedule
-int g_conv_dyn = 1;
-// msu_conv_mode bit 1 (default off; the A/B handle of tools and tests, no environment switch):
-// widths other than 96 take the generic kernels
-int g_conv_generic_wide = 0;
-
-template <typename T, int NCT, int KS, int NW, int MT, bool WDB, bool IN_D2S, bool IN_GELU, bool OUT_D2S,
-          bool OUT_GGRAD, bool BIAS, bool DUAL>
-int launch_v2(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S,
-              bf16_t* Y, bf16_t* Y2, hipStream_t st) {
-  constexpr int PS = KS * 16 + 8, TH = NW * MT;
-  constexpr size_t lds = sizeof(bf16_t) * ((size_t)(TH + 2) * 34 * PS + (WDB ? 2 : 1) * (size_t)NCT * 32 * PS);
-  static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv3x3_v2_kernel<T, NCT, KS, NW, MT, WDB, IN_D2S, IN_GELU, OUT_D2S, OUT_GGRAD, BIAS, DUAL>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  const long ntiles = (long)g.B * ((g.W + 31) / 32) * ((g.H + TH - 1) / TH);
-  if (ntiles == 0) return 0;
-  // 32-bit element offsets inside the kernel
-  if ((long)g.B * g.H * g.W * (g.Cin > g.Cout ? g.Cin : g.Cout) >= (1L << 31)) return -2;
-  const int grid = (int)(ntiles < msu_num_cus() ? ntiles : msu_num_cus());
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, st, X, Wt, bias, S, Y, Y2, g, (int)ntiles);
-  return MSU_CHECK_LAUNCH();
+// The width of the persistent LDS-DMA kernels (conv3x3_v3_kernel, conv3x3_wgrad_v2_kernel) that
+// serves 16-bit Cin -> Cout, or 0: the generic kernels.  The one routing rule of both
+// translation units; generic_wide is msu_conv_mode bit 1 (msu_conv3x3_route passes false: it
+// reports what is built).  conv3x3_v3_kernel has no GELU on load: those forms stay generic.
+inline int persistent_width(bool is16, int Cin, int Cout, bool generic_wide) {
+  if (!is16 || Cin != Cout) return 0;
+  if (Cin == 96) return 96;
+  return Cin == 128 && !generic_wide ? 128 : 0;
 }
 
-template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL, bool SPREAD, bool M16,
-          int CW = 96, int TWW = 32>
-int launch_v3s(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S, bf16_t* Y,
-               bf16_t* Y2, hipStream_t st) {
-  using G = V3W<CW, TWW>;
+// msu_conv3x3_route: bit 0 the forward / backward-data launches, bit 1 the weight gradient.
+inline int conv_route(bool is16, int Cin, int Cout) { return persistent_width(is16, Cin, Cout, false) ? 3 : 0; }
+
+template <typename T, int C, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL>
+int launch_v3(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S, bf16_t* Y,
+              bf16_t* Y2, hipStream_t st) {
+  // C = 96: forward launches on 16x16x32 MFMA (same tile, LDS images and schedule; (p >> 1) & 3
+  // swizzle), since round 4: same-box kbench (r04b) conv1 2.22-2.28 vs 2.44 ms, conv2 1.48 vs
+  // 1.55 ms (bare MFMA loops of this shape run at ~1.12-1.15x the FLOP/s of 32x32x16 on MI355X at
+  // equal cycles: the clock it holds, MI355X_MICROARCH.md).  The dgrad keeps 32x32x16: with its
+  // GELU' operands held from tap 7 the 16x16 form spills 260 B per lane.  Halo loads spread over
+  // taps 1..7 (SPREAD; all at tap 1 measured equal, r03).  v4 (one wave per SIMD, 4 rows per
+  // wave) was 7-10 % slower on every launch (r03l/m) and is gone.
+  // C = 128 (Swin-B decoder head): 8-row tiles, every launch on 16x16x32 MFMA -- with one row per
+  // wave only that shape lets a weight fragment feed two MFMAs, and the dgrad's accumulators (64)
+  // and GELU' operands (32 registers) are fewer than at 96, so it does not spill there.
+  // (ablation 2048: the C = 96 dgrad on 16 x 16 x 32 too; ablation 8192: C = 128 on the 16-row x
+  // 16-pixel geometry, two rows per wave)
+  constexpr bool M16 = !(C == 96 && OUT_GGRAD) || (MSU_EXP & 2048) != 0;
+  constexpr int TWW = (C == 128 && (MSU_EXP & 8192) != 0) ? 16 : 32;
+  using G = V3W<C, TWW>;
   constexpr size_t lds = G::LDS;
-  auto kern = conv3x3_v3_kernel<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, SPREAD, M16, CW, TWW>;
+  auto kern = conv3x3_v3_kernel<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, true, M16, C, TWW>;
   const long ntiles = (long)g.B * ((g.W + G::TWV - 1) / G::TWV) * ((g.H + G::TH - 1) / G::TH);
   if (ntiles == 0) return 0;
   // 32-bit element offsets and tile indices inside the kernel (checked before any HIP call)
-  if ((long)g.B * g.H * g.W * CW >= (1L << 31)) return -2;
+  if ((long)g.B * g.H * g.W * C >= (1L << 31)) return -2;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1611,59 +1364,20 @@ int launch_v3s(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float
   return MSU_CHECK_LAUNCH();
 }
 
-template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL>
-int launch_v3(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S, bf16_t* Y,
-              bf16_t* Y2, hipStream_t st) {
-  // Forward launches on 16x16x32 MFMA (same tile, LDS images and schedule; (p >> 1) & 3
-  // swizzle), since round 4: same-box kbench (r04b) conv1 2.22-2.28 vs 2.44 ms, conv2 1.48 vs
-  // 1.55 ms (bare MFMA loops of this shape run at ~1.12-1.15x the FLOP/s of 32x32x16 on MI355X at
-  // equal cycles: the clock it holds, MI355X_MICROARCH.md).  The dgrad keeps 32x32x16: with its
-  // GELU' operands held from tap 7 the 16x16 form spills 260 B per lane.  Halo loads spread over
-  // taps 1..7 (SPREAD; all at tap 1 measured equal, r03).  v4 (one wave per SIMD, 4 rows per
-  // wave) was 7-10 % slower on every launch (r03l/m) and is gone.
-  // (ablation 2048: the dgrad on 16 x 16 x 32 too)
-  if constexpr (!OUT_GGRAD || (MSU_EXP & 2048) != 0)
-    return launch_v3s<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, true, true>(g, X, Wt, bias, S, Y, Y2, st);
-  return launch_v3s<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, true, false>(g, X, Wt, bias, S, Y, Y2, st);
-}
-
-// C = 128 (Swin-B decoder head): 8-row tiles, every launch on 16x16x32 MFMA -- with one row per
-// wave only that shape lets a weight fragment feed two MFMAs, and the dgrad's accumulators (64)
-// and GELU' operands (32 registers) are fewer than at 96, so it does not spill there.
-template <typename T, bool IN_D2S, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL>
-int launch_v3_128(const ConvGeom& g, const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* S,
-                  bf16_t* Y, bf16_t* Y2, hipStream_t st) {
-  // (ablation 8192: the 16-row x 16-pixel geometry, two rows per wave)
-  return launch_v3s<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL, true, true, 128, (MSU_EXP & 8192) ? 16 : 32>(g, X, Wt, bias, S, Y,
-                                                                                                     Y2, st);
-}
-
-// Which (dtype, Cin, Cout) take a persistent LDS-DMA kernel (msu_conv3x3_route): bit 0 the
-// forward / backward-data launches, bit 1 the weight gradient.
-inline int conv_route(bool is16, int Cin, int Cout) {
-  if (!is16 || Cin != Cout) return 0;
-  return Cin == 96 || Cin == 128 ? 3 : 0;
-}
-
+// persistent width ? launch_v3<C> : the generic kernel by output width
 template <typename T, bool IN_D2S, bool IN_GELU, bool OUT_D2S, bool OUT_GGRAD, bool BIAS, bool DUAL = false>
 int conv_nt(const ConvGeom& g, const void* X, const void* Wt, const float* bias, const void* S,
             void* Y, void* Y2, hipStream_t st) {
   const T* x = (const T*)X; const T* w = (const T*)Wt; const T* s = (const T*)S; T* y = (T*)Y; T* y2 = (T*)Y2;
   if constexpr (sizeof(T) == 2 && !IN_GELU) {
-    if (g.Cout == 96 && g.CinP == 96 && g.Cin == 96)
-      return launch_v3<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(g, (const bf16_t*)x, (const bf16_t*)w, bias,
-                                                                  (const bf16_t*)s, (bf16_t*)y, (bf16_t*)y2, st);
-    if (g.Cout == 128 && g.CinP == 128 && g.Cin == 128 && !g_conv_generic_wide)
-      return launch_v3_128<T, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(g, (const bf16_t*)x, (const bf16_t*)w, bias,
-                                                                      (const bf16_t*)s, (bf16_t*)y, (bf16_t*)y2, st);
-  }
-  if constexpr (sizeof(T) == 2) {
-    // the Swin-T/S decoder head width takes the persistent v2 kernel
-    if (g.Cout == 96 && g.CinP == 96)
-      return launch_v2<T, 3, 6, 8, 1, true, IN_D2S, IN_GELU, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(g, (const bf16_t*)x,
-                                                                                          (const bf16_t*)w, bias,
-                                                                                          (const bf16_t*)s, (bf16_t*)y,
-                                                                                          (bf16_t*)y2, st);
+    auto v3 = [&](auto C) {
+      return launch_v3<T, decltype(C)::value, IN_D2S, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(
+          g, (const bf16_t*)x, (const bf16_t*)w, bias, (const bf16_t*)s, (bf16_t*)y, (bf16_t*)y2, st);
+    };
+    switch (persistent_width(true, g.Cin, g.Cout, g_conv_generic_wide != 0)) {
+      case 96: return v3(IC<96>{});
+      case 128: return v3(IC<128>{});
+    }
   }
   switch (g.Cout / 16) {
     case 1: return launch_conv<T, 1, IN_D2S, IN_GELU, OUT_D2S, OUT_GGRAD, BIAS, DUAL>(g, x, w, bias, s, y, y2, st);

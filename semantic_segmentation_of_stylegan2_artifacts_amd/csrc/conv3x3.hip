@@ -1,7 +1,9 @@
 // Refine-conv forward and backward-data entry points (kernels: conv3x3.h).
 #include "conv3x3.h"
 
-int conv3x3_generic_wide() { return g_conv_generic_wide; }
+// msu_conv_mode bits 0 and 1 (declared in conv3x3.h)
+int g_conv_dyn = 1;
+int g_conv_generic_wide = 0;
 
 extern "C" {
 

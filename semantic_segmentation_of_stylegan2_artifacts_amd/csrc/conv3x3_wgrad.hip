@@ -37,12 +37,12 @@ int msu_conv3x3_wgrad2(int dtype, int in_mode, const void* X, const void* dY, fl
   int nsum = nchunk;  // partial chunks to sum
   // the widths with a persistent kernel (conv3x3_wgrad_v2_kernel); at 128 one co half per
   // workgroup, so nchunk / 2 partial chunks
-  const bool v2 = msu_is16(dtype) && Cin == Cout && (Cin == 96 || (Cin == 128 && !conv3x3_generic_wide()));
-  if (v2) {
+  const int pw = persistent_width(msu_is16(dtype), Cin, Cout, g_conv_generic_wide != 0);
+  if (pw) {
     const bf16_t* x = (const bf16_t*)X; const bf16_t* d = (const bf16_t*)dY;
     MSU_DISPATCH16(dtype, T, rc = with_in_mode(in_mode, [&](auto D2S, auto GL) {
       constexpr bool d2s = decltype(D2S)::value, gl = decltype(GL)::value;
-      return Cin == 96 ? launch_wgrad_v2<T, 96, d2s, gl>(g, x, d, part, dbpart, nchunk, st)
+      return pw == 96 ? launch_wgrad_v2<T, 96, d2s, gl>(g, x, d, part, dbpart, nchunk, st)
                        : launch_wgrad_v2<T, 128, d2s, gl>(g, x, d, part, dbpart, nchunk, st);
     }));
     if (rc > 0) { nsum = rc; rc = 0; }

@@ -1,7 +1,8 @@
 """Run-to-run determinism of the eager training step under switches, in one process.
 
-For each configuration (weight-gradient side stream on / off, GEMM route default / lib, conv
-kernel v3 / v2 is a build-time env and not switched here) run the swinT224 Trainer N times from
+For each configuration (weight-gradient side stream on / off, GEMM route default / lib; the
+refine convs have one kernel per width, conv3x3_v3_kernel at 96 / 128, and nothing to switch
+here) run the swinT224 Trainer N times from
 the same weights (lr = 0: every step computes the same gradient into the AdamW moments) and
 count the distinct final moment vectors; list the parameters that differ between runs.
 
