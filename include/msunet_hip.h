@@ -399,6 +399,15 @@ int msu_adamw_dev2(float* p, float* g, float* m, float* v, long n, const double*
 /* hyper[1] += 1 unless found_inf[0] != 0 (the skipped step does not count, as torch's AdamW
  * `step` state is not advanced when GradScaler skips optimizer.step). */
 int msu_step_advance(double* hyper, const float* found_inf, void* stream);
+/* msu_step_advance under a loss scale (GradScaler.update, trainer.py:182,316), one launch, in
+ * this order: inv_out[0] = (inv_world ? inv_world[0] : 1) / scale[0] (the scale this step's
+ * backward used: what msu_adamw_dev2 takes as inv_scale next); found_inf[0] != 0: scale *= backoff,
+ * growth_tracker = 0, the step is not counted; else hyper[1] += 1 and torch._amp_update_scale_'s
+ * growth rule (x growth after `interval` clean steps in a row, unless the grown scale is not
+ * finite).  scale f32 [1], growth_tracker i32 [1]; growth >= 1, 0 < backoff <= 1, interval >= 1. */
+int msu_loss_scale_step(double* hyper, const float* found_inf, float* scale, int* growth_tracker,
+                        const float* inv_world, float* inv_out, double growth, double backoff, int interval,
+                        void* stream);
 /* flag[0] = 1 if any element of x (x0[0:n0], x1[0:n1]) is inf/NaN; flag zeroed by the caller
  * (GradScaler's non-finite check, torch._amp_foreach_non_finite_check_and_unscale_). */
 int msu_nonfinite(const float* x, long n, float* flag, void* stream);

@@ -42,11 +42,16 @@ def save_best(model, epoch, best_score, log_save_path, name="best_model.pth"):
     return best_path
 
 
-def save_last(model, optimizer_state, epoch, iter_num, dice, log_save_path):
-    """trainer.py:403-409 (``epoch_<n>.pth``)."""
+def save_last(model, optimizer_state, epoch, iter_num, dice, log_save_path, scaler_state=None):
+    """trainer.py:403-409 (``epoch_<n>.pth``).  scaler_state (``Trainer.scaler_state_dict()``, the
+    f16 loss scale in ``GradScaler.state_dict()`` format) adds a ``"scaler"`` key; without one the
+    payload is the reference's, key for key."""
     path = os.path.join(log_save_path, "epoch_" + str(epoch) + ".pth")
-    torch.save({"epoch": epoch, "model": _cpu_state(core(model)), "optimizer": optimizer_state,
-                "iter_num": iter_num, "dice": dice}, path)
+    payload = {"epoch": epoch, "model": _cpu_state(core(model)), "optimizer": optimizer_state,
+               "iter_num": iter_num, "dice": dice}
+    if scaler_state:
+        payload["scaler"] = dict(scaler_state)
+    torch.save(payload, path)
     return path
 
 

@@ -283,6 +283,32 @@ __global__ void step_advance_kernel(double* hyper, const float* found_inf) {
   if (threadIdx.x == 0 && !(found_inf && found_inf[0] != 0.f)) hyper[1] = hyper[1] + 1.0;
 }
 
+// step_advance with a loss scale (one thread): the unscale factor AdamW reads next, from the
+// scale this step's backward used, then torch._amp_update_scale_'s rule on {scale, tracker}
+// (ATen amp_update_scale_cuda_kernel: the products are formed in double and rounded to float
+// once, a grown scale that is not finite is dropped, the tracker restarts either way)
+__global__ void loss_scale_step_kernel(double* hyper, const float* found_inf, float* scale, int* tracker,
+                                       const float* inv_world, float* inv_out, double growth, double backoff,
+                                       int interval) {
+  if (threadIdx.x != 0) return;
+  const float s = scale[0];
+  inv_out[0] = (inv_world ? inv_world[0] : 1.f) / s;
+  if (found_inf[0] != 0.f) {
+    scale[0] = (float)((double)s * backoff);
+    tracker[0] = 0;
+    return;
+  }
+  hyper[1] = hyper[1] + 1.0;
+  const int successful = tracker[0] + 1;
+  if (successful == interval) {
+    const float grown = (float)((double)s * growth);
+    if (isfinite(grown)) scale[0] = grown;
+    tracker[0] = 0;
+  } else {
+    tracker[0] = successful;
+  }
+}
+
 // any non-finite in x0[0:n0] or x1[0:n1] -> flag[0] = 1 (flag zeroed by the caller)
 __global__ void __launch_bounds__(256) nonfinite2_kernel(const float* x0, long n0, const float* x1, long n1,
                                                          float* flag) {
@@ -509,6 +535,17 @@ int msu_adamw_dev2(float* p, float* g, float* m, float* v, long n, const double*
 int msu_step_advance(double* hyper, const float* found_inf, void* stream) {
   if (hyper == nullptr) return -2;
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, found_inf);
+  return MSU_CHECK_LAUNCH();
+}
+
+int msu_loss_scale_step(double* hyper, const float* found_inf, float* scale, int* growth_tracker,
+                        const float* inv_world, float* inv_out, double growth, double backoff, int interval,
+                        void* stream) {
+  if (hyper == nullptr || found_inf == nullptr || scale == nullptr || growth_tracker == nullptr ||
+      inv_out == nullptr || interval < 1 || !(growth >= 1.0) || !(backoff > 0.0 && backoff <= 1.0))
+    return -2;
+  hipLaunchKernelGGL(loss_scale_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, found_inf, scale,
+                     growth_tracker, inv_world, inv_out, growth, backoff, interval);
   return MSU_CHECK_LAUNCH();
 }
 

@@ -1133,6 +1133,11 @@ def gemm_route(M, N, K, epi=TOK_PLAIN):
             r = "nt"
         elif _ROUTE_FORCE == "ntmlp" and epi != TOK_PLAIN and nt_supported(M, N, K):
             r = "nt"
+        elif _ROUTE_FORCE == "" and tok and epi != TOK_PLAIN and M >= 65536:
+            # an epilogue GEMM the NT GEMM does not cover (K = 96: the x4 expand + GELU of one
+            # 1024^2 image, 65 536 tokens) stays on the token GEMM down to the M at which stage 0
+            # takes its production routes (_LINBWD_MIN_M), not the library GEMM + a GELU pass
+            r = "tok"
         else:
             r = "lib"
         _tok_cache[key] = r
@@ -2154,3 +2159,17 @@ def adamw_dev_(param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2, eps, weigh
 def step_advance_(hyper, found_inf=None):
     """hyper[1] += 1 unless found_inf[0] != 0 (a skipped step is not counted)."""
     _lib.call("msu_step_advance", _p(hyper), _p(found_inf), _s(hyper))
+
+
+def loss_scale_step_(hyper, found_inf, scale, growth_tracker, inv_out, inv_world=None, growth=2.0, backoff=0.5,
+                     interval=2000):
+    """step_advance_ under a loss scale, one launch: inv_out = (inv_world or 1) / scale for the
+    AdamW launches that follow, then GradScaler.update() on the device (found_inf: scale x
+    backoff, tracker 0, step not counted; else hyper[1] += 1 and torch._amp_update_scale_'s
+    growth rule).  scale / inv_out f32 [1], growth_tracker i32 [1]."""
+    _need_cuda(hyper, found_inf, scale, growth_tracker, inv_out)
+    if scale.dtype != torch.float32 or inv_out.dtype != torch.float32 or growth_tracker.dtype != torch.int32 \
+            or found_inf.dtype != torch.float32 or hyper.dtype != torch.float64 or hyper.numel() < 2:
+        raise ValueError("loss_scale_step_: hyper f64 [2], found_inf / scale / inv_out f32 [1], growth_tracker i32 [1]")
+    _lib.call("msu_loss_scale_step", _p(hyper), _p(found_inf), _p(scale), _p(growth_tracker), _p(inv_world),
+              _p(inv_out), float(growth), float(backoff), int(interval), _s(hyper))

@@ -6,8 +6,9 @@ AdamW (two param groups, ``trainer.py:130-152``) -> ``loss.item()``; multi-GPU v
 sampler requires batch_size == 2).
 
 Here:
-* one process per GPU (torchrun env), bf16 autocast (no loss scaling needed), no host
-  synchronisation inside the step (the loss stays on the device);
+* one process per GPU (torchrun env), bf16 autocast (no loss scaling needed) or f16 autocast
+  with a device-side loss scale (``loss_scale="dynamic"``: GradScaler's rule, run inside the
+  step), no host synchronisation inside the step (the loss stays on the device);
 * trainable parameters and their gradients live in two flat f32 buffers (weight-decay /
   no-decay, the reference's split rule) laid out in reverse registration order, so
   gradients become ready roughly front-to-back during backward;
@@ -60,7 +61,7 @@ def cosine_lr(epoch, base_lr, warmup_epochs, max_epochs, warmup_lr, min_lr, warm
 class FlatGroup:
     """Parameters (and grads) of one optimizer group re-homed into flat f32 buffers."""
 
-    def __init__(self, named_params, weight_decay, device):
+    def __init__(self, named_params, weight_decay, device, shadow_dtype=torch.bfloat16):
         self.names = [n for n, _ in named_params]
         self.params = [p for _, p in named_params]
         self.weight_decay = weight_decay
@@ -78,9 +79,9 @@ class FlatGroup:
         self.grad = torch.zeros(n, device=device, dtype=torch.float32)
         self.exp_avg = torch.zeros_like(self.data)
         self.exp_avg_sq = torch.zeros_like(self.data)
-        # bf16 shadow of the parameters, refreshed once per step: the Linear ops read it
-        # instead of casting every weight at every call
-        self.shadow = torch.empty(n, device=device, dtype=torch.bfloat16)
+        # 16-bit shadow of the parameters (the trainer's compute dtype, bf16 or f16), refreshed
+        # once per step: the Linear ops read it instead of casting every weight at every call
+        self.shadow = torch.empty(n, device=device, dtype=shadow_dtype)
         for p, off in zip(self.params, self.offsets):
             k = p.numel()
             self.data[off:off + k].copy_(p.detach().reshape(-1))
@@ -89,7 +90,7 @@ class FlatGroup:
             p._msu_shadow = self.shadow[off:off + k].view_as(p)
             p._msu_shadow_ver = -1  # not valid until the first refresh
             p._msu_direct = True  # backward kernels accumulate straight into p.grad
-        # transposed bf16 shadow of the 2-D weights (Linear weights: both dims multiples of 8),
+        # transposed 16-bit shadow of the 2-D weights (Linear weights: both dims multiples of 8),
         # written by one batched transpose after each refresh: the input-gradient GEMMs read
         # W^T in the forward GEMM's layout instead of transposing per call (ops._shadow_t)
         tab, owners, toff, tiles = [], [], 0, 0
@@ -103,13 +104,13 @@ class FlatGroup:
         self.tshadow = self.ttable = None
         self.ntiles = tiles
         if tab and torch.device(device).type == "cuda":
-            self.tshadow = torch.empty(toff, device=device, dtype=torch.bfloat16)
+            self.tshadow = torch.empty(toff, device=device, dtype=shadow_dtype)
             self.ttable = torch.tensor(tab, dtype=torch.int64).to(device)
             for (_, to, N, K, _), p in zip(tab, owners):
                 p._msu_shadow_t = self.tshadow[to:to + N * K].view(K, N)
 
     def refresh_shadow(self):
-        """Re-cast the bf16 shadow after the master weights changed (AdamW writes them through
+        """Re-cast the 16-bit shadow after the master weights changed (AdamW writes them through
         a raw pointer).  Each parameter records its version: an in-place write made through
         the parameter itself (load_state_dict, ``p.copy_``) bumps it and makes the Linear ops
         cast that weight again until the next refresh."""
@@ -145,7 +146,7 @@ class GradBucketer:
     # GradScaler defaults (torch.amp.GradScaler): the fp16 wire's dynamic scale
     INIT_SCALE, GROWTH_FACTOR, BACKOFF_FACTOR, GROWTH_INTERVAL = 2.0 ** 16, 2.0, 0.5, 2000
 
-    def __init__(self, groups, bucket_bytes, process_group=None, wire_dtype=None):
+    def __init__(self, groups, bucket_bytes, process_group=None, wire_dtype=None, own_scale=True):
         self.pg = process_group
         # wire_dtype (bf16 / f16): each bucket is cast into a persistent 16-bit buffer, summed
         # over the ranks in that precision and cast back into the f32 gradients -- half the
@@ -158,10 +159,13 @@ class GradBucketer:
         # cast (tiny gradients stay above f16's 6e-8 underflow) and divided by it on the way
         # back; a sum that overflows comes back inf, the trainer's non-finite check skips the
         # step on every rank and update_scale() halves the scale (x2 after 2000 clean steps).
-        # bf16 keeps f32's exponent range: no scale.
+        # bf16 keeps f32's exponent range: no scale.  own_scale=False: the gradients arrive
+        # already scaled (the trainer's f16 loss scale, the reference's arrangement exactly), so
+        # the buckets are cast as they are; an overflowing sum reaches the trainer's non-finite
+        # check after the all-reduce and every rank skips and backs its loss scale off together.
         dev = groups[0].grad.device
         self.scale = self.inv_scale = self.growth_tracker = None
-        if self.wire_dtype == torch.float16:
+        if self.wire_dtype == torch.float16 and own_scale:
             self.scale = torch.full((1,), self.INIT_SCALE, device=dev, dtype=torch.float32)
             self.inv_scale = torch.full((1,), 1.0 / self.INIT_SCALE, device=dev, dtype=torch.float32)
             self.growth_tracker = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -304,6 +308,23 @@ class GradBucketer:
         torch.reciprocal(self.scale, out=self.inv_scale)
 
 
+def loss_scale_rule(scale, tracker, found_inf, growth=2.0, backoff=0.5, interval=2000):
+    """Host restatement of ``torch._amp_update_scale_`` (GradScaler.update), the rule
+    ``msu_loss_scale_step`` runs on the device: (scale, tracker) after a step whose gradients
+    were non-finite (found_inf) or clean.  The scale is an f32: products round to f32, and a
+    grown scale that is no longer finite is dropped (the tracker restarts either way)."""
+    def f32(v):
+        return torch.tensor(v, dtype=torch.float64).to(torch.float32).item()
+    scale = f32(scale)
+    if found_inf:
+        return f32(scale * backoff), 0
+    tracker += 1
+    if tracker != interval:
+        return scale, tracker
+    grown = f32(scale * growth)
+    return (grown if math.isfinite(grown) else scale), 0
+
+
 def reseed(seed, rank=0):
     """Per-rank randomness for data parallelism: the model is built from the shared seed
     (identical initial weights on every rank), then every rank draws its own drop-path and
@@ -339,11 +360,31 @@ def rccl_capture_blocker(process_group):
 class Trainer:
     def __init__(self, model, config, device, lr=None, amp_dtype=torch.bfloat16, bucket_mb=32,
                  world_size=1, process_group=None, rank=0, seed=None, skip_nonfinite=True, use_graph=None,
-                 graph_warmup=4, grad_wire_dtype=None, always_reduce=False):
+                 graph_warmup=4, grad_wire_dtype=None, always_reduce=False, loss_scale=None, init_scale=65536.0,
+                 growth_interval=2000):
         self.model = model
         self.device = device
         self.amp_dtype = amp_dtype
         self.rank = rank
+        # loss_scale: None (no scale: the backward seed is 1), "dynamic" (GradScaler's
+        # rule from init_scale: x0.5 on a non-finite step, x2 after growth_interval clean ones) or
+        # a float (a static scale: the same path with both factors 1).  f16 only: its 5 exponent
+        # bits flush small activation gradients to zero at seed 1; bf16 and f32 need no scale.
+        if loss_scale is not None:
+            if amp_dtype != torch.float16:
+                raise ValueError(f"loss_scale is for amp_dtype=torch.float16, not {amp_dtype}")
+            if not skip_nonfinite:
+                raise ValueError("loss_scale needs skip_nonfinite=True: an overflowing step must be skipped")
+            if loss_scale == "dynamic":
+                start, self.scale_factors = float(init_scale), (2.0, 0.5)
+            elif isinstance(loss_scale, (int, float)) and not isinstance(loss_scale, bool):
+                start, self.scale_factors = float(loss_scale), (1.0, 1.0)
+            else:
+                raise ValueError(f"loss_scale must be None, 'dynamic' or a number, got {loss_scale!r}")
+            if not (math.isfinite(start) and start > 0) or int(growth_interval) < 1:
+                raise ValueError(f"loss scale {start} / growth_interval {growth_interval}: need a finite "
+                                 "positive scale and an interval >= 1")
+        self.growth_interval = int(growth_interval)
         if seed is not None:
             reseed(seed, rank)
         core = model.ms_unet if hasattr(model, "ms_unet") else model
@@ -357,8 +398,10 @@ class Trainer:
                 continue
             (no_decay if is_no_decay(name, p) else decay).append((name, p))
         # reverse registration order ~ gradient-ready order during backward
-        self.groups = [FlatGroup(decay[::-1], config.TRAIN.WEIGHT_DECAY, device),
-                       FlatGroup(no_decay[::-1], 0.0, device)]
+        self.amp16 = amp_dtype in (torch.bfloat16, torch.float16)
+        sdt = amp_dtype if self.amp16 else torch.bfloat16
+        self.groups = [FlatGroup(decay[::-1], config.TRAIN.WEIGHT_DECAY, device, sdt),
+                       FlatGroup(no_decay[::-1], 0.0, device, sdt)]
         # the dead branches' parameters are never updated: one 16-bit shadow each for the run, so
         # their no-grad forwards (side stream) read it instead of casting every weight every step
         # (16 cast launches per step at Swin-T); a write through the parameter (load_state_dict)
@@ -380,6 +423,14 @@ class Trainer:
         self.skip_nonfinite = skip_nonfinite
         self.found_inf = torch.zeros(1, device=device, dtype=torch.float32)
         self._one = torch.ones((), device=device, dtype=torch.float32)
+        # the device-side loss scale: backward's seed, updated inside the step (replayable);
+        # inv_out = inv_world / scale of the step in flight, what AdamW unscales by
+        self.scale = self.growth_tracker = self.inv_out = None
+        if loss_scale is not None:
+            self.scale = torch.full((1,), start, device=device, dtype=torch.float32)
+            self.growth_tracker = torch.zeros(1, device=device, dtype=torch.int32)
+            self.inv_out = torch.zeros(1, device=device, dtype=torch.float32)
+            self._seed = self.scale.view(())
         t = config.TRAIN
         self.loss_fn = DynamicLoss(alpha=t.TVERSKY_LOSS_ALPHA, beta=t.TVERSKY_LOSS_BETA,
                                    tversky_bce_mix=t.LOSS_TVERSKY_BCE_MIX)
@@ -390,7 +441,9 @@ class Trainer:
         self.inv_world = torch.full((1,), 1.0 / world_size, device=device, dtype=torch.float32)
         # always_reduce: the bucketed all-reduce even for one rank (a 1-rank RCCL group exercises
         # the product DP path on one GPU)
-        self.reducer = (GradBucketer(self.groups, int(bucket_mb * (1 << 20)), process_group, grad_wire_dtype)
+        # under a loss scale the gradients on the f16 wire are already scaled: no second scale
+        self.reducer = (GradBucketer(self.groups, int(bucket_mb * (1 << 20)), process_group, grad_wire_dtype,
+                                     own_scale=loss_scale is None)
                         if world_size > 1 or always_reduce else None)
         # HIP-graph replay of the step (see step()).  use_graph: True / False, or None = the
         # MSU_GRAPH environment switch: "1" always, "0" never, "auto" (default) = capture only
@@ -435,6 +488,39 @@ class Trainer:
     def optimizer_steps(self):
         """AdamW steps actually applied (skipped non-finite steps excluded); syncs."""
         return int(self.hyper[1].item())
+
+    def loss_scale(self):
+        """The current loss scale (None without one); syncs."""
+        return None if self.scale is None else float(self.scale.item())
+
+    def scaler_state_dict(self):
+        """The loss-scale state in ``torch.amp.GradScaler.state_dict()`` format ({} without a
+        scale, as a disabled GradScaler's); syncs."""
+        if self.scale is None:
+            return {}
+        return {"scale": self.loss_scale(), "growth_factor": self.scale_factors[0],
+                "backoff_factor": self.scale_factors[1], "growth_interval": self.growth_interval,
+                "_growth_tracker": int(self.growth_tracker.item())}
+
+    def load_scaler_state_dict(self, sd):
+        """Inverse of scaler_state_dict; takes a ``torch.amp.GradScaler.state_dict()`` as is.  The
+        factors and the interval are launch arguments: a captured step is dropped when they change."""
+        if self.scale is None:
+            if sd:
+                raise RuntimeError("this trainer has no loss scale to load a scaler state into")
+            return
+        if not sd:
+            raise RuntimeError("empty scaler state (saved from a disabled GradScaler)")
+        factors = (float(sd["growth_factor"]), float(sd["backoff_factor"]))
+        interval = int(sd["growth_interval"])
+        scale = float(sd["scale"])
+        if not (math.isfinite(scale) and scale > 0 and factors[0] >= 1.0 and 0.0 < factors[1] <= 1.0 and interval >= 1):
+            raise ValueError(f"unusable scaler state {sd}")
+        if (factors, interval) != (self.scale_factors, self.growth_interval):
+            self.invalidate_graph()
+        self.scale_factors, self.growth_interval = factors, interval
+        self.scale.fill_(scale)
+        self.growth_tracker.fill_(int(sd["_growth_tracker"]))
 
     def skipped_steps(self):
         """Training steps whose update was skipped (non-finite gradients); syncs."""
@@ -519,7 +605,8 @@ class Trainer:
         After ``graph_warmup`` eager steps (lazy library / kernel-attribute initialisation,
         the all-reduce accumulation counts of step 0), the whole device side of the step --
         forward, DynamicLoss, backward with its side-stream work, the bucketed all-reduce,
-        the non-finite check, AdamW, the gradient reset and the bf16 shadow refresh -- is
+        the non-finite check, the loss-scale update, AdamW, the gradient reset and the 16-bit shadow
+        refresh -- is
         captured once into a HIP graph and replayed: one launch per step instead of ~1300.
         Inputs are copied into the graph's static buffers; dropout keeps drawing fresh masks
         (device-side seed counter, drop-path pools redrawn inside the graph)."""
@@ -553,14 +640,17 @@ class Trainer:
             self._flag_reset_by_loss = ops.step_flag_reset()
         finally:
             ops.set_step_flag(None)
-        loss.backward(self._one)  # a persistent seed: no ones_like fill per step
+        # a persistent seed: no ones_like fill per step.  Under a loss scale the seed is the
+        # device scale itself (msu_dynloss_bwd2 reads it from memory): every gradient of this
+        # backward is scale x the true one, the returned loss stays unscaled
+        loss.backward(self._one if self.scale is None else self._seed)
         if self.reducer is not None:
             self.reducer.finish()
         ops.join_side_streams()  # weight gradients issued on the side stream
         inv = self.inv_world if self.world_size > 1 else None
-        bf16 = self.amp_dtype == torch.bfloat16
-        if bf16:
-            # the bf16 shadow's parameter versions are marked now, while the GPU still has
+        amp16 = self.amp16
+        if amp16:
+            # the 16-bit shadow's parameter versions are marked now, while the GPU still has
             # backward work queued, not after the last launch of the step (it left the GPU idle
             # there); the shadow itself is refreshed after AdamW below
             for g in self.groups:
@@ -576,15 +666,22 @@ class Trainer:
             ops.nonfinite_(self.groups[0].grad, found, self.groups[1].grad)
             if wire_scaled:
                 self.reducer.update_scale(found)
-        ops.step_advance_(self.hyper, found)
+        if self.scale is None:
+            ops.step_advance_(self.hyper, found)
+        else:
+            # the same single launch also runs GradScaler.update() on the device: inv_out from
+            # the scale this backward used, then the scale's backoff / growth for the next step
+            ops.loss_scale_step_(self.hyper, found, self.scale, self.growth_tracker, self.inv_out, inv,
+                                 self.scale_factors[0], self.scale_factors[1], self.growth_interval)
+            inv = self.inv_out
         for g in self.groups:
-            # the gradient reset and (bf16) the shadow refresh ride in AdamW's pass: no fill and
+            # the gradient reset and (16-bit) the shadow refresh ride in AdamW's pass: no fill and
             # no re-read of the parameters for the cast (a skipped step leaves the shadow as is
             # and zeroes the gradient too)
             ops.adamw_dev_(g.data, g.grad, g.exp_avg, g.exp_avg_sq, self.hyper, self.betas[0], self.betas[1],
                            self.eps, g.weight_decay, inv_scale=inv, found_inf=found,
-                           shadow=g.shadow if bf16 else None, zero_grad=True)
-            if bf16:  # keeps evaluation between steps on the updated weights
+                           shadow=g.shadow if amp16 else None, zero_grad=True)
+            if amp16:  # keeps evaluation between steps on the updated weights
                 g.transpose_shadow()
         return loss.detach()
 
@@ -605,7 +702,7 @@ class Trainer:
         self.graph_mode = "1" if self.use_graph else "0"
 
     def _eager_step(self, images, labels):
-        if self.amp_dtype == torch.bfloat16 and not self._shadow_fresh:
+        if self.amp16 and not self._shadow_fresh:
             for g in self.groups:
                 g.refresh_shadow()
         self._shadow_fresh = False
@@ -622,7 +719,7 @@ class Trainer:
         self.step_count += 1
         # the next step's refresh is skipped; a write through a parameter in between bumps its
         # version and the Linear ops cast that weight themselves (ops._shadow)
-        self._shadow_fresh = self.amp_dtype == torch.bfloat16
+        self._shadow_fresh = self.amp16
         return loss
 
     def _param_versions(self):
@@ -633,7 +730,7 @@ class Trainer:
         blocker = rccl_capture_blocker(self.reducer.pg) if self.reducer is not None else None
         if blocker:  # use_graph forced on after construction: refuse instead of aborting later
             raise RuntimeError(f"cannot capture the training step: {blocker}")
-        if self.amp_dtype == torch.bfloat16 and not self._shadow_fresh:
+        if self.amp16 and not self._shadow_fresh:
             for g in self.groups:
                 g.refresh_shadow()
         self._sx = images.detach().clone()
@@ -703,8 +800,8 @@ class Trainer:
         v = self._param_versions()
         if v != self._versions:
             # a write through a parameter (load_state_dict, p.copy_) since the last step: the
-            # captured forward reads the bf16 shadow, so re-derive it before replaying
-            if self.amp_dtype == torch.bfloat16:
+            # captured forward reads the 16-bit shadow, so re-derive it before replaying
+            if self.amp16:
                 for g in self.groups:
                     g.refresh_shadow()
             self._versions = v
