@@ -13,14 +13,18 @@
 #include "common.h"
 #include "reduce.h"
 
-// MSU_EXP: ablation bits for timing experiments only (tools/build_exp.sh); 0 in every real build
-#ifndef MSU_EXP
-#define MSU_EXP 0
-#endif
-
 namespace {
 
 enum InMode { IN_PLAIN = 0, IN_ADD = 1, IN_MERGE = 2, IN_D2S2 = 3 };
+// the statement with the constant M set to a run-time mode (as MSU_DISPATCH does for a dtype);
+// falls through for an unknown mode
+#define LN_MODE(mode, M, ...)                                            \
+  switch (mode) {                                                        \
+    case IN_PLAIN: { constexpr int M = IN_PLAIN; __VA_ARGS__; } break;   \
+    case IN_ADD: { constexpr int M = IN_ADD; __VA_ARGS__; } break;       \
+    case IN_MERGE: { constexpr int M = IN_MERGE; __VA_ARGS__; } break;   \
+    case IN_D2S2: { constexpr int M = IN_D2S2; __VA_ARGS__; } break;     \
+  }
 
 // 16-byte row chunks: 4 f32 or 8 16-bit elements per lane access
 template <typename T> struct VecW;
@@ -29,17 +33,19 @@ template <> struct VecW<float> {
   static MSU_DEV void load(const float* p, float (&v)[4]) { Vec4<float>::load(p, v); }
   static MSU_DEV void store(float* p, const float (&v)[4]) { Vec4<float>::store(p, v); }
 };
+// the 8 elements of a 16-bit chunk held in registers (Q: uint4 or u32x4)
+template <typename T, typename Q>
+MSU_DEV void unpack16(const Q q, float (&v)[8]) {
+  const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = Fmt16<T>::lo(w[i]);
+    v[2 * i + 1] = Fmt16<T>::hi(w[i]);
+  }
+}
 template <typename T> struct VecW16 {
   static constexpr int W = 8;
-  static MSU_DEV void load(const T* p, float (&v)[8]) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = Fmt16<T>::lo(w[i]);
-      v[2 * i + 1] = Fmt16<T>::hi(w[i]);
-    }
-  }
+  static MSU_DEV void load(const T* p, float (&v)[8]) { unpack16<T>(*reinterpret_cast<const uint4*>(p), v); }
   static MSU_DEV void store(T* p, const float (&v)[8]) {
     uint4 q;
     q.x = pack2<T>(v[0], v[1]);
@@ -100,109 +106,85 @@ MSU_DEV long src_off(const LnArgs& a, long r, int col) {
   }
 }
 
-template <typename T>
-MSU_DEV void unpack16(const uint4 q, float (&v)[8]) {
-  const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = Fmt16<T>::lo(w[i]);
-    v[2 * i + 1] = Fmt16<T>::hi(w[i]);
-  }
-}
+// Rows of one 16-bit chunk per lane (every C <= 512 of the path) are software-prefetched: the
+// group's next row is loaded while this one is worked on, and the lane's gamma / beta stay in
+// registers across rows.  The row arithmetic is written once per direction; it takes its
+// operands through small loaders that read the prefetched registers or memory.
+template <typename T, int KMAX>
+constexpr bool ln_prefetch = KMAX == 1 && VecW<T>::W == 8;
 
-template <typename T, int MODE, int TPR, int KMAX, bool PFF = true>
+template <typename T, int MODE, int TPR, int KMAX>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(LnArgs a) {
   constexpr int VW = VecW<T>::W;  // elements per 16-B chunk
+  constexpr bool PF = ln_prefetch<T, KMAX>;
   const int lane = threadIdx.x % TPR;
   const int grp = threadIdx.x / TPR;
   constexpr int GPB = 256 / TPR;
   const int nchunk = a.C / VW;
   const T* X = reinterpret_cast<const T*>(a.x);
   const T* Bv = reinterpret_cast<const T*>(a.b);
-  // 16-bit rows of one chunk per lane: the group's next row is loaded while this one is
-  // normalised (same arithmetic as the plain loop below; see ln_bwd_kernel)
-  if constexpr (KMAX == 1 && VW == 8 && PFF) {
-    const int ch = lane;
-    const bool act = ch < nchunk;
-    float g[VW], bt[VW];
-    if (act) {
-      load_f32<VW>(a.gamma + ch * VW, g);
-      load_f32<VW>(a.beta + ch * VW, bt);
-    }
-    const long stride = (long)gridDim.x * GPB;
-    long r = (long)blockIdx.x * GPB + grp;
-    uint4 qx{}, qb{};
-    float qsc = 1.f;
-    auto fetch = [&](long rr) __attribute__((always_inline)) {
-      if constexpr (MODE == IN_ADD) {
-        if (a.bscale) qsc = a.bscale[rr / a.rows_per_sample];
-      }
-      if (act) {
-        const long off = src_off<MODE>(a, rr, ch * VW);
-        qx = *reinterpret_cast<const uint4*>(X + off);
-        if constexpr (MODE == IN_ADD) {
-          if (Bv) qb = *reinterpret_cast<const uint4*>(Bv + off);
-        }
-      }
-    };
-    if (r < a.rows) fetch(r);
-    for (; r < a.rows; r += stride) {
-      const uint4 cx = qx, cb = qb;
-      const float sc = qsc;
-      if (r + stride < a.rows) fetch(r + stride);
-      float v[VW];
-      float sum = 0.f;
-      if (act) {
-        unpack16<T>(cx, v);
-        if constexpr (MODE == IN_ADD) {
-          if (Bv) {
-            float w[VW];
-            unpack16<T>(cb, w);
-#pragma unroll
-            for (int e = 0; e < VW; ++e) v[e] += sc * w[e];
-          }
-#pragma unroll
-          for (int e = 0; e < VW; ++e) v[e] = to_f32(from_f32<T>(v[e]));
-          if (a.s_out) VecW<T>::store(reinterpret_cast<T*>(a.s_out) + src_off<MODE>(a, r, ch * VW), v);
-        }
-#pragma unroll
-        for (int e = 0; e < VW; ++e) sum += v[e];
-      }
-      sum = group_sum<TPR>(sum);
-      const float mu = sum / a.C;
-      float var = 0.f;
-      if (act) {
-#pragma unroll
-        for (int e = 0; e < VW; ++e) { const float d = v[e] - mu; var += d * d; }
-      }
-      var = group_sum<TPR>(var);
-      const float rs = rsqrtf(var / a.C + a.eps);
-      if (act) {
-        float o[VW];
-#pragma unroll
-        for (int e = 0; e < VW; ++e) o[e] = (v[e] - mu) * rs * g[e] + bt[e];
-        VecW<T>::store(reinterpret_cast<T*>(a.y) + r * (long)a.C + ch * VW, o);
-      }
-      if (lane == 0) { a.mean[r] = mu; a.rstd[r] = rs; }
-    }
-  } else
-  for (long r = (long)blockIdx.x * GPB + grp; r < a.rows; r += (long)gridDim.x * GPB) {
-    float v[KMAX][VW];
-    float sum = 0.f;
-    float sc = 1.f;
+  const long stride = (long)gridDim.x * GPB;
+  long r = (long)blockIdx.x * GPB + grp;
+  // PF only: the lane's gamma / beta, and the next row's chunks and stochastic-depth scale
+  const bool act = lane < nchunk;
+  float pg[VW], pbt[VW];
+  uint4 qx{}, qb{};
+  float qsc = 1.f;
+  auto fetch = [&](long rr) __attribute__((always_inline)) {
     if constexpr (MODE == IN_ADD) {
+      if (a.bscale) qsc = a.bscale[rr / a.rows_per_sample];
+    }
+    if (act) {
+      const long off = src_off<MODE>(a, rr, lane * VW);
+      qx = *reinterpret_cast<const uint4*>(X + off);
+      if constexpr (MODE == IN_ADD) {
+        if (Bv) qb = *reinterpret_cast<const uint4*>(Bv + off);
+      }
+    }
+  };
+  if constexpr (PF) {
+    if (act) {
+      load_f32<VW>(a.gamma + lane * VW, pg);
+      load_f32<VW>(a.beta + lane * VW, pbt);
+    }
+    if (r < a.rows) fetch(r);
+  }
+  for (; r < a.rows; r += stride) {
+    uint4 cx{}, cb{};
+    float sc = 1.f;
+    if constexpr (PF) {
+      cx = qx; cb = qb; sc = qsc;
+      if (r + stride < a.rows) fetch(r + stride);
+    } else if constexpr (MODE == IN_ADD) {
       if (a.bscale) sc = a.bscale[r / a.rows_per_sample];
     }
+    auto xin = [&](long off, float (&v)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) unpack16<T>(cx, v); else VecW<T>::load(X + off, v);
+    };
+    auto bin = [&](long off, float (&w)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) unpack16<T>(cb, w); else VecW<T>::load(Bv + off, w);
+    };
+    auto affine = [&](int ch, float (&g)[VW], float (&bt)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) { g[e] = pg[e]; bt[e] = pbt[e]; }
+      } else {
+        load_f32<VW>(a.gamma + ch * VW, g);
+        load_f32<VW>(a.beta + ch * VW, bt);
+      }
+    };
+    float v[KMAX][VW];
+    float sum = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
       const int ch = lane + k * TPR;
       if (ch < nchunk) {
         const long off = src_off<MODE>(a, r, ch * VW);
-        VecW<T>::load(X + off, v[k]);
+        xin(off, v[k]);
         if constexpr (MODE == IN_ADD) {
           if (Bv) {
             float w[VW];
-            VecW<T>::load(Bv + off, w);
+            bin(off, w);
 #pragma unroll
             for (int e = 0; e < VW; ++e) v[k][e] += sc * w[e];
           }
@@ -235,8 +217,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnArgs a) {
       const int ch = lane + k * TPR;
       if (ch < nchunk) {
         float o[VW], g[VW], bt[VW];
-        load_f32<VW>(a.gamma + ch * VW, g);
-        load_f32<VW>(a.beta + ch * VW, bt);
+        affine(ch, g, bt);
 #pragma unroll
         for (int e = 0; e < VW; ++e) o[e] = (v[k][e] - mu) * rs * g[e] + bt[e];
         VecW<T>::store(Y + r * (long)a.C + ch * VW, o);
@@ -272,12 +253,14 @@ struct LnBwdArgs {
   const void* dres3 = nullptr;
 };
 
-template <typename T, int MODE, int TPR, int KMAX, bool PFB = true>
+template <typename T, int MODE, int TPR, int KMAX>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
-  // no implicit contraction: the two row loops below (prefetching / plain) fuse exactly the
-  // multiply-adds written as fmaf, so they agree bitwise (tools/ln_pf_check.py)
+  // no implicit contraction: exactly the multiply-adds written as fmaf are fused, so the
+  // rounding of every output is fixed by the source and not by how the compiler schedules a
+  // variant (prefetched or not, any KMAX)
 #pragma clang fp contract(off)
   constexpr int VW = VecW<T>::W;  // elements per 16-B chunk
+  constexpr bool PF = ln_prefetch<T, KMAX>;
   const int lane = threadIdx.x % TPR;
   const int grp = threadIdx.x / TPR;
   constexpr int GPB = 256 / TPR;
@@ -292,120 +275,64 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
   LnArgs fa;
   fa.C = a.C; fa.H = a.H; fa.W = a.W; fa.Cin = a.Cin;
   constexpr bool HAS_RES = MODE == IN_ADD || MODE == IN_PLAIN;
-  // 16-bit rows of one chunk per lane (every C <= 512 of the path): the group's next row is
-  // loaded while this one is reduced and stored, so a group waits one memory round trip per
-  // row only where the prefetch has not landed (the arithmetic, and so the result, is the
-  // plain loop's below).  A/B switch: the plain loop, template-selected by launch_bwd
-  if constexpr (KMAX == 1 && VW == 8 && PFB) {
-    const int ch = lane;
-    const bool act = ch < nchunk;
-    float gg[VW];
-    if (act) load_f32<VW>(a.gamma + ch * VW, gg);
-    const long stride = (long)gridDim.x * GPB;
-    long r = (long)blockIdx.x * GPB + grp;
-    struct RowSet {
-      uint4 x{}, d{}, r{}, r2{}, r3{};
-      float mu = 0.f, rs = 0.f;
-    };
-    auto fetch = [&](RowSet& q, long rr) __attribute__((always_inline)) {
-      q.mu = a.mean[rr];
-      q.rs = a.rstd[rr];
-      if (act) {
-        const long off = src_off<MODE>(fa, rr, ch * VW);
-        q.x = *reinterpret_cast<const uint4*>(X + off);
-        q.d = *reinterpret_cast<const uint4*>(DY + rr * (long)a.C + ch * VW);
-        if constexpr (HAS_RES) {
-          if (a.dres) q.r = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.dres) + off);
-          if (a.dres2) q.r2 = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.dres2) + off);
-          if (a.dres3) q.r3 = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.dres3) + off);
-        }
-      }
-    };
-    auto work = [&](const RowSet& c, long r) __attribute__((always_inline)) {
-      float xh[VW], g[VW];
-      float s1 = 0.f, s2 = 0.f;
-      if (act) {
-        float xv[VW], dv[VW];
-        unpack16<T>(c.x, xv);
-        unpack16<T>(c.d, dv);
+  const T* RES[3] = {reinterpret_cast<const T*>(a.dres), reinterpret_cast<const T*>(a.dres2),
+                     reinterpret_cast<const T*>(a.dres3)};
+  const long stride = (long)gridDim.x * GPB;
+  long r = (long)blockIdx.x * GPB + grp;
+  // PF only: the lane's gamma and the next row (x, dy, the residual gradients, mean, rstd), so a
+  // group waits one memory round trip per row only where the prefetch has not landed
+  const bool act = lane < nchunk;
+  float pgg[VW];
+  struct RowSet {
+    uint4 x{}, d{}, res[3]{};
+    float mu = 0.f, rs = 0.f;
+  };
+  auto fetch = [&](RowSet& q, long rr) __attribute__((always_inline)) {
+    q.mu = a.mean[rr];
+    q.rs = a.rstd[rr];
+    if (act) {
+      const long off = src_off<MODE>(fa, rr, lane * VW);
+      q.x = *reinterpret_cast<const uint4*>(X + off);
+      q.d = *reinterpret_cast<const uint4*>(DY + rr * (long)a.C + lane * VW);
+      if constexpr (HAS_RES) {
 #pragma unroll
-        for (int e = 0; e < VW; ++e) {
-          xh[e] = (xv[e] - c.mu) * c.rs;
-          g[e] = dv[e] * gg[e];
-          s1 += g[e];
-          s2 = __builtin_fmaf(g[e], xh[e], s2);
-          accg[0][e] = __builtin_fmaf(dv[e], xh[e], accg[0][e]);
-          accb[0][e] += dv[e];
-        }
-      }
-      s1 = group_sum<TPR>(s1) / a.C;
-      s2 = group_sum<TPR>(s2) / a.C;
-      float sc = 1.f;
-      if constexpr (MODE == IN_ADD) {
-        if (a.bscale) sc = a.bscale[r / a.rows_per_sample];
-      }
-      if (act) {
-        float o[VW];
-#pragma unroll
-        for (int e = 0; e < VW; ++e) o[e] = __builtin_fmaf(-xh[e], s2, g[e] - s1);
-        const long off = src_off<MODE>(fa, r, ch * VW);
-        bool res = false;
-        if constexpr (HAS_RES) res = a.dres != nullptr;
-        if (res) {
-          float dr[VW];
-          unpack16<T>(c.r, dr);
-#pragma unroll
-          for (int e = 0; e < VW; ++e) o[e] = __builtin_fmaf(c.rs, o[e], dr[e]);
-          if (a.dres2) {
-            unpack16<T>(c.r2, dr);
-#pragma unroll
-            for (int e = 0; e < VW; ++e) o[e] += dr[e];
-          }
-          if (a.dres3) {
-            unpack16<T>(c.r3, dr);
-#pragma unroll
-            for (int e = 0; e < VW; ++e) o[e] += dr[e];
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < VW; ++e) o[e] *= c.rs;
-        }
-        VecW<T>::store(reinterpret_cast<T*>(a.dx) + off, o);
-        if constexpr (MODE == IN_ADD) {
-          if (a.db) {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) o[e] *= sc;
-            VecW<T>::store(reinterpret_cast<T*>(a.db) + off, o);
-          }
-        }
-      }
-    };
-    if constexpr ((MSU_EXP & 256) != 0) {
-      // ablation: two rows ahead (two register sets, the loop unrolled by two)
-      RowSet q0, q1;
-      if (r < a.rows) fetch(q0, r);
-      if (r + stride < a.rows) fetch(q1, r + stride);
-      for (; r < a.rows; r += 2 * stride) {
-        work(q0, r);
-        if (r + 2 * stride < a.rows) fetch(q0, r + 2 * stride);
-        if (r + stride >= a.rows) break;
-        work(q1, r + stride);
-        if (r + 3 * stride < a.rows) fetch(q1, r + 3 * stride);
-      }
-    } else {
-      RowSet nxt;
-      if (r < a.rows) fetch(nxt, r);
-      for (; r < a.rows; r += stride) {
-        const RowSet cur = nxt;
-        if (r + stride < a.rows) fetch(nxt, r + stride);
-        work(cur, r);
+        for (int i = 0; i < 3; ++i)
+          if (RES[i]) q.res[i] = *reinterpret_cast<const uint4*>(RES[i] + off);
       }
     }
-  } else
-  for (long r = (long)blockIdx.x * GPB + grp; r < a.rows; r += (long)gridDim.x * GPB) {
-    const float mu = a.mean[r], rs = a.rstd[r];
+  };
+  RowSet nxt;
+  if constexpr (PF) {
+    if (act) load_f32<VW>(a.gamma + lane * VW, pgg);
+    if (r < a.rows) fetch(nxt, r);
+  }
+  // one row: cur holds its mean / rstd and, when prefetched, its chunks.  (A lambda, not the loop's
+  // body: written inline the prefetching kernels took 8 to 10 more VGPRs and four of them fell an
+  // occupancy step, profiles/r17a_ln_resources.txt)
+  auto row = [&](const RowSet& cur, long r) __attribute__((always_inline)) {
+    const float mu = cur.mu, rs = cur.rs;
+    auto xin = [&](long off, float (&v)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) unpack16<T>(cur.x, v); else VecW<T>::load(X + off, v);
+    };
+    auto dyin = [&](int ch, float (&v)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) unpack16<T>(cur.d, v); else VecW<T>::load(DY + r * (long)a.C + ch * VW, v);
+    };
+    auto resin = [&](int i, long off, float (&v)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) unpack16<T>(cur.res[i], v); else VecW<T>::load(RES[i] + off, v);
+    };
+    auto gin = [&](int ch, float (&v)[VW]) __attribute__((always_inline)) {
+      if constexpr (PF) {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) v[e] = pgg[e];
+      } else {
+        load_f32<VW>(a.gamma + ch * VW, v);
+      }
+    };
     float xh[KMAX][VW], g[KMAX][VW];
-    // the residual gradient is loaded with x and dy: one memory round trip per row, not two
+    // dres from memory is read with x and dy: one memory round trip per row, not two (a prefetched
+    // one is already in registers and is unpacked where it is added).  dres2 / dres3 (the
+    // skip-gradient handoff only) are read where they are added: held from here they would cost
+    // the wide variants KMAX * VW registers each
     float dr[KMAX][VW];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -414,12 +341,12 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
       if (ch < nchunk) {
         float xv[VW], dv[VW], gg[VW];
         const long off = src_off<MODE>(fa, r, ch * VW);
-        VecW<T>::load(X + off, xv);
-        VecW<T>::load(DY + r * (long)a.C + ch * VW, dv);
-        if constexpr (HAS_RES) {
-          if (a.dres) VecW<T>::load(reinterpret_cast<const T*>(a.dres) + off, dr[k]);
+        xin(off, xv);
+        dyin(ch, dv);
+        if constexpr (HAS_RES && !PF) {
+          if (RES[0]) resin(0, off, dr[k]);
         }
-        load_f32<VW>(a.gamma + ch * VW, gg);
+        gin(ch, gg);
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
           xh[k][e] = (xv[e] - mu) * rs;
@@ -446,16 +373,16 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
         for (int e = 0; e < VW; ++e) o[e] = __builtin_fmaf(-xh[k][e], s2, g[k][e] - s1);
         const long off = src_off<MODE>(fa, r, ch * VW);
         bool res = false;
-        if constexpr (HAS_RES) res = a.dres != nullptr;
+        if constexpr (HAS_RES) res = RES[0] != nullptr;
         if (res) {
+          if constexpr (PF) resin(0, off, dr[k]);  // already in registers: unpacked where it is used
 #pragma unroll
           for (int e = 0; e < VW; ++e) o[e] = __builtin_fmaf(rs, o[e], dr[k][e]);
-          const void* more[2] = {a.dres2, a.dres3};
 #pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            if (more[q]) {
+          for (int q = 1; q < 3; ++q) {
+            if (RES[q]) {
               float d2[VW];
-              VecW<T>::load(reinterpret_cast<const T*>(more[q]) + off, d2);
+              resin(q, off, d2);
 #pragma unroll
               for (int e = 0; e < VW; ++e) o[e] += d2[e];
             }
@@ -474,6 +401,17 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
         }
       }
     }
+  };
+  for (; r < a.rows; r += stride) {
+    RowSet cur;
+    if constexpr (PF) {
+      cur = nxt;
+      if (r + stride < a.rows) fetch(nxt, r + stride);
+    } else {
+      cur.mu = a.mean[r];
+      cur.rs = a.rstd[r];
+    }
+    row(cur, r);
   }
   // parameter-gradient partials: the row groups of a wave hold the same columns in the
   // same lanes -> fixed xor-shuffle tree over the groups, then the 4 waves' rows are summed
@@ -533,14 +471,14 @@ int launch_fwd(const LnArgs& a, hipStream_t st, int max_blocks) {
   // up to C = 128, +0.25 % more up to C = 512 (r01, 3 of 3 pairs); the next row of a group
   // prefetched (r04y: +0.2 %)
   if (nchunk <= 16) return go(ln_fwd_kernel<T, MODE, 16, 1>, 16);
-  if constexpr ((MSU_EXP & 8) != 0) {  // ablation: C = 192 rows as 8 lanes x 3 chunks
-    if (nchunk <= 24 && nchunk > 16) return go(ln_fwd_kernel<T, MODE, 8, 3>, 8);
-  }
   if (nchunk <= 32) return go(ln_fwd_kernel<T, MODE, 32, 1>, 32);
   if (nchunk <= 64) return go(ln_fwd_kernel<T, MODE, 64, 1>, 64);
   if (nchunk <= 32 * 4) return go(ln_fwd_kernel<T, MODE, 32, 4>, 32);
   if (nchunk <= 64 * 4) return go(ln_fwd_kernel<T, MODE, 64, 4>, 64);
-  if (nchunk <= 64 * 8) return go(ln_fwd_kernel<T, MODE, 64, 8>, 64);
+  // shape_ok caps C at 2048: only 4-element chunks get past 256 of them
+  if constexpr (VecW<T>::W == 4) {
+    if (nchunk <= 64 * 8) return go(ln_fwd_kernel<T, MODE, 64, 8>, 64);
+  }
   return -2;
 }
 
@@ -557,7 +495,9 @@ int launch_bwd(const LnBwdArgs& a, hipStream_t st, int nblocks) {
   if (nchunk <= 64) return go(ln_bwd_kernel<T, MODE, 64, 1>);
   if (nchunk <= 32 * 4) return go(ln_bwd_kernel<T, MODE, 32, 4>);
   if (nchunk <= 64 * 4) return go(ln_bwd_kernel<T, MODE, 64, 4>);
-  if (nchunk <= 64 * 8) return go(ln_bwd_kernel<T, MODE, 64, 8>);
+  if constexpr (VecW<T>::W == 4) {
+    if (nchunk <= 64 * 8) return go(ln_bwd_kernel<T, MODE, 64, 8>);
+  }
   return -2;
 }
 
@@ -584,8 +524,7 @@ int fwd_dispatch(int dtype, const LnArgs& a, hipStream_t st) {
   // overlap loads with the normalisation; at 16384 the C >= 192 launches ran one row per group
   // (r05af alone: 131072 x 192 add-LN 43.3 vs 51.5 us, 32768 x 384 22.9 vs 25.0; step 172.3 vs
   // 171.8 img/s, 3 of 3 pairs, r05ag; r01, before the prefetch, had 16384 ahead of 4096)
-  constexpr int cap = (MSU_EXP & 16) ? 2048 : ((MSU_EXP & 64) ? 1024 : ((MSU_EXP & 32) ? 16384 : 4096));
-  MSU_DISPATCH(dtype, T, return launch_fwd<T, MODE>(a, st, cap));
+  MSU_DISPATCH(dtype, T, return launch_fwd<T, MODE>(a, st, 4096));
   return -3;
 }
 
@@ -606,9 +545,9 @@ int bwd_dispatch(int dtype, const LnBwdArgs& a, float* dgamma, float* dbeta, int
   // dgamma and dbeta null: only the [nparts][2C] partials are written (the caller reduces them
   // later, msu_colsum_batch: the deferred LayerNorm parameter gradients)
   const bool partials_only = dgamma == nullptr && dbeta == nullptr;
-  if (partials_only || (MSU_EXP & 128) != 0) b.tail = -1;  // (128: ablation, no reduction)
+  if (partials_only) b.tail = -1;
   MSU_DISPATCH(dtype, T, rc = launch_bwd<T, MODE>(b, st, nparts));
-  if (rc || b.tail >= 0 || partials_only || (MSU_EXP & 128)) return rc;
+  if (rc || b.tail >= 0 || partials_only) return rc;
   if (dbeta == dgamma + a.C) {  // contiguous [dgamma | dbeta]: one reduction launch
     colsum(a.part, nparts, 2L * a.C, 2L * a.C, dgamma, accumulate, st);
   } else {
@@ -769,12 +708,7 @@ __global__ void __launch_bounds__(256) head_fwd16_kernel(const T* z, const float
       const long r = r0 + h < rows ? r0 + h : r0;
 #pragma unroll
       for (int k = 0; k < KC; ++k) {
-        const u32x4 q = *reinterpret_cast<const u32x4*>(z + r * C + (lane + TPR * k) * 8);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          v[h][k][2 * i] = Fmt16<T>::lo(q[i]);
-          v[h][k][2 * i + 1] = Fmt16<T>::hi(q[i]);
-        }
+        unpack16<T>(*reinterpret_cast<const u32x4*>(z + r * C + (lane + TPR * k) * 8), v[h][k]);
       }
     }
 #pragma unroll
@@ -970,8 +904,7 @@ int msu_ln_part_blocks(long rows, int C) {
   // (512 / 256: 168.2 / 162.5 vs 170.0 img/s, r04t); C >= 384 (stages 2-3, whose partials are 2C
   // wide and whose reductions run on the main stream): 512 (170.5 / 170.4 vs 169.8 / 169.8 with
   // 1024, 256: 168.7 / 168.6; r04v)
-  constexpr long cap = (MSU_EXP & 2) ? 4096 : ((MSU_EXP & 1) ? 2048 : 1024);
-  constexpr long cap_deep = (MSU_EXP & 2) ? 2048 : ((MSU_EXP & 1) ? 1024 : 512);
+  constexpr long cap = 1024, cap_deep = 512;
   long nb = (rows + 15) / 16;
   if (nb > cap) nb = cap;
   if (C >= 384 && nb > cap_deep) nb = cap_deep;
@@ -984,30 +917,7 @@ int msu_layernorm_fwd(int dtype, int mode, const void* x, const void* b, const f
                       float eps, void* stream) {
   LnArgs a{x, b, bscale, s_out, gamma, beta, y, mean, rstd, rows, C, H, W, Cin,
            rows_per_sample > 0 ? rows_per_sample : 1, eps};
-  hipStream_t st = (hipStream_t)stream;
-  switch (mode) {
-    case IN_PLAIN: return fwd_dispatch<IN_PLAIN>(dtype, a, st);
-    case IN_ADD: return fwd_dispatch<IN_ADD>(dtype, a, st);
-    case IN_MERGE: return fwd_dispatch<IN_MERGE>(dtype, a, st);
-    case IN_D2S2: return fwd_dispatch<IN_D2S2>(dtype, a, st);
-  }
-  return -3;
-}
-
-int msu_layernorm_bwd(int dtype, int mode, const void* dy, const void* x, const void* dres,
-                      const float* gamma, const float* mean, const float* rstd, void* dx,
-                      void* db, const float* bscale, long rows_per_sample, float* part,
-                      int nparts, float* dgamma, float* dbeta, long rows, int C, int H, int W,
-                      int Cin, int accumulate, void* stream) {
-  LnBwdArgs a{dy, x, dres, gamma, mean, rstd, dx, db, bscale, part, rows, C, H, W, Cin,
-              rows_per_sample > 0 ? rows_per_sample : 1};
-  hipStream_t st = (hipStream_t)stream;
-  switch (mode) {
-    case IN_PLAIN: return bwd_dispatch<IN_PLAIN>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-    case IN_ADD: return bwd_dispatch<IN_ADD>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-    case IN_MERGE: return bwd_dispatch<IN_MERGE>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-    case IN_D2S2: return bwd_dispatch<IN_D2S2>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-  }
+  LN_MODE(mode, M, return fwd_dispatch<M>(dtype, a, (hipStream_t)stream));
   return -3;
 }
 
@@ -1021,14 +931,17 @@ int msu_layernorm_bwd3(int dtype, int mode, const void* dy, const void* x, const
               rows_per_sample > 0 ? rows_per_sample : 1};
   a.dres2 = dres2;
   a.dres3 = dres3;
-  hipStream_t st = (hipStream_t)stream;
-  switch (mode) {
-    case IN_PLAIN: return bwd_dispatch<IN_PLAIN>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-    case IN_ADD: return bwd_dispatch<IN_ADD>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-    case IN_MERGE: return bwd_dispatch<IN_MERGE>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-    case IN_D2S2: return bwd_dispatch<IN_D2S2>(dtype, a, dgamma, dbeta, nparts, accumulate, st);
-  }
+  LN_MODE(mode, M, return bwd_dispatch<M>(dtype, a, dgamma, dbeta, nparts, accumulate, (hipStream_t)stream));
   return -3;
+}
+
+int msu_layernorm_bwd(int dtype, int mode, const void* dy, const void* x, const void* dres,
+                      const float* gamma, const float* mean, const float* rstd, void* dx,
+                      void* db, const float* bscale, long rows_per_sample, float* part,
+                      int nparts, float* dgamma, float* dbeta, long rows, int C, int H, int W,
+                      int Cin, int accumulate, void* stream) {
+  return msu_layernorm_bwd3(dtype, mode, dy, x, dres, nullptr, nullptr, gamma, mean, rstd, dx, db, bscale,
+                            rows_per_sample, part, nparts, dgamma, dbeta, rows, C, H, W, Cin, accumulate, stream);
 }
 
 int msu_tail_reduce_mode(int mode) {

@@ -447,34 +447,48 @@ def _ln_setup(ctx, inputs, output):
     ctx.set_materialize_grads(False)
 
 
+def _ln_bwd_plain(ctx, dy, mode, rows, C, H, W, Cin):
+    """(dx, dweight, dbias) of a LayerNorm without residual gradients, for any input mode of
+    csrc/layernorm.hip; the parameter gradients are None where they went straight into .grad."""
+    x, w, mean, rstd = ctx.saved_tensors
+    dy = _as(dy, x.dtype)
+    dx = torch.empty_like(x)
+    dw, db, acc, direct = _ln_grads(ctx, C, x.device)
+    n, part = _ln_parts(rows, C, x.device)
+    _lib.call("msu_layernorm_bwd", _dt(x), mode, _p(dy), _p(x), None, _p(w), _p(mean), _p(rstd),
+              _p(dx), None, None, 1, _p(part), n, _p(dw), _p(db), rows, C, H, W, Cin, acc, _s(x))
+    if direct:
+        _ln_finish(ctx, part, n, C)
+        return dx, None, None
+    return dx, dw, db
+
+
 def _ln_backward(ctx, dy, _dm, _dr):
     global res_handoff_calls
     x, w, mean, rstd = ctx.saved_tensors
     res = _take(ctx.handoff)  # the other readers' gradients of x (the paired add-LN's first)
     if dy is None:
         return (functools.reduce(torch.add, res) if res else None), None, None, None, None
-    dy = _as(dy, x.dtype)
     C = x.shape[-1]
     rows = x.numel() // C
+    if not res:
+        return _ln_bwd_plain(ctx, dy, IN_PLAIN, rows, C, 0, 0, 0) + (None, None)
+    dy = _as(dy, x.dtype)
     dx = torch.empty_like(x)
     dw, db, acc, direct = _ln_grads(ctx, C, x.device)
     n, part = _ln_parts(rows, C, x.device)
-    if res:
-        # the add-mode backward: dx = LN'(dy) + res (+ res2 + res3) in one pass, one rounding
-        # (no branch output: scale null; a fourth reader's gradient, not on the model's path, is
-        # folded in by an add first)
-        res = [_as(r, x.dtype).contiguous() for r in res]
-        if len(res) > 3:
-            res = res[:2] + [functools.reduce(torch.add, res[2:])]
-        res_handoff_calls += 1
-        r2 = res[1] if len(res) > 1 else None
-        r3 = res[2] if len(res) > 2 else None
-        _lib.call("msu_layernorm_bwd3", _dt(x), IN_ADD, _p(dy), _p(x), _p(res[0]), _p(r2), _p(r3), _p(w),
-                  _p(mean), _p(rstd), _p(dx), None, None, rows // x.shape[0], _p(part), n, _p(dw), _p(db), rows, C,
-                  0, 0, 0, acc, _s(x))
-    else:
-        _lib.call("msu_layernorm_bwd", _dt(x), IN_PLAIN, _p(dy), _p(x), None, _p(w), _p(mean), _p(rstd),
-                  _p(dx), None, None, 1, _p(part), n, _p(dw), _p(db), rows, C, 0, 0, 0, acc, _s(x))
+    # the add-mode backward: dx = LN'(dy) + res (+ res2 + res3) in one pass, one rounding
+    # (no branch output: scale null; a fourth reader's gradient, not on the model's path, is
+    # folded in by an add first)
+    res = [_as(r, x.dtype).contiguous() for r in res]
+    if len(res) > 3:
+        res = res[:2] + [functools.reduce(torch.add, res[2:])]
+    res_handoff_calls += 1
+    r2 = res[1] if len(res) > 1 else None
+    r3 = res[2] if len(res) > 2 else None
+    _lib.call("msu_layernorm_bwd3", _dt(x), IN_ADD, _p(dy), _p(x), _p(res[0]), _p(r2), _p(r3), _p(w),
+              _p(mean), _p(rstd), _p(dx), None, None, rows // x.shape[0], _p(part), n, _p(dw), _p(db), rows, C,
+              0, 0, 0, acc, _s(x))
     if direct:
         _ln_finish(ctx, part, n, C)
         return dx, None, None, None, None
@@ -567,95 +581,51 @@ def add_layer_norm(a, branch, scale, weight, bias, eps=1e-5, handoff=0):
     return s, y
 
 
-def _merge_ln_impl(x, w, b, eps):
+def _gather_geom(mode, x):
+    """(rows, C, H, W, Cin) of the LayerNorm that gathers its rows from x [B, H, W, c] (src_off in
+    csrc/layernorm.hip): merge [B, HW/4, 4c], depth-to-space [B, 4HW, c/4]; y is [B, rows / B, C]."""
+    B, H, W, c = x.shape
+    if mode == IN_MERGE:
+        return B * (H // 2) * (W // 2), 4 * c, H, W, c
+    return B * 4 * H * W, c // 4, H, W, 0
+
+
+def _gather_ln_impl(mode, x, w, b, eps):
     _need_cuda(x)
     x = x.contiguous()
-    B, H, W, C = x.shape
-    rows = B * (H // 2) * (W // 2)
-    y = torch.empty(B, rows // B, 4 * C, device=x.device, dtype=x.dtype)
+    rows, C, H, W, Cin = _gather_geom(mode, x)
+    y = torch.empty(x.shape[0], rows // x.shape[0], C, device=x.device, dtype=x.dtype)
     mean, rstd = _stats(x, rows)
-    _lib.call("msu_layernorm_fwd", _dt(x), IN_MERGE, _p(x), None, None, 1, None, _p(w), _p(b),
-              _p(y), _p(mean), _p(rstd), rows, 4 * C, H, W, C, eps, _s(x))
+    _lib.call("msu_layernorm_fwd", _dt(x), mode, _p(x), None, None, 1, None, _p(w), _p(b),
+              _p(y), _p(mean), _p(rstd), rows, C, H, W, Cin, eps, _s(x))
     return y, mean, rstd
 
 
-def _merge_ln_fake(x, w, b, eps):
-    B, H, W, C = x.shape
-    rows = B * (H // 2) * (W // 2)
-    return (x.new_empty(B, rows // B, 4 * C), x.new_empty(rows, dtype=torch.float32),
+def _gather_ln_fake(mode, x, w, b, eps):
+    rows, C = _gather_geom(mode, x)[:2]
+    return (x.new_empty(x.shape[0], rows // x.shape[0], C), x.new_empty(rows, dtype=torch.float32),
             x.new_empty(rows, dtype=torch.float32))
 
 
-def _merge_ln_backward(ctx, dy, _dm, _dr):
-    x, w, mean, rstd = ctx.saved_tensors
+def _gather_ln_backward(mode, ctx, dy, _dm, _dr):
     if dy is None:
         return None, None, None, None
-    B, H, W, C = x.shape
-    rows = B * (H // 2) * (W // 2)
-    dy = _as(dy, x.dtype)
-    dx = torch.empty_like(x)
-    dw, db, acc, direct = _ln_grads(ctx, 4 * C, x.device)
-    n, part = _ln_parts(rows, 4 * C, x.device)
-    _lib.call("msu_layernorm_bwd", _dt(x), IN_MERGE, _p(dy), _p(x), None, _p(w), _p(mean), _p(rstd),
-              _p(dx), None, None, 1, _p(part), n, _p(dw), _p(db), rows, 4 * C, H, W, C, acc, _s(x))
-    if direct:
-        _ln_finish(ctx, part, n, 4 * C)
-        return dx, None, None, None
-    return dx, dw, db, None
+    return _ln_bwd_plain(ctx, dy, mode, *_gather_geom(mode, ctx.saved_tensors[0])) + (None,)
 
 
-_merge_layer_norm = _define("merge_layer_norm",
-                            "(Tensor x, Tensor weight, Tensor bias, float eps) -> (Tensor, Tensor, Tensor)",
-                            _merge_ln_impl, _merge_ln_fake, _ln_setup, _merge_ln_backward)
+def _define_gather_ln(name, mode):
+    return _define(name, "(Tensor x, Tensor weight, Tensor bias, float eps) -> (Tensor, Tensor, Tensor)",
+                   functools.partial(_gather_ln_impl, mode), functools.partial(_gather_ln_fake, mode), _ln_setup,
+                   functools.partial(_gather_ln_backward, mode))
+
+
+_merge_layer_norm = _define_gather_ln("merge_layer_norm", IN_MERGE)
+_d2s_layer_norm = _define_gather_ln("d2s_layer_norm", IN_D2S2)
 
 
 def merge_layer_norm(x, weight, bias, eps=1e-5):
     """PatchMerging gather (x0,x1,x2,x3 order) + LayerNorm(4C): [B,H,W,C] -> [B,HW/4,4C]."""
     return _merge_layer_norm(_as(x, act_dtype()), _f32(weight), _f32(bias), float(eps))[0]
-
-
-def _d2s_ln_impl(x, w, b, eps):
-    _need_cuda(x)
-    x = x.contiguous()
-    B, H, W, C4 = x.shape
-    c = C4 // 4
-    rows = B * 4 * H * W
-    y = torch.empty(B, 4 * H * W, c, device=x.device, dtype=x.dtype)
-    mean, rstd = _stats(x, rows)
-    _lib.call("msu_layernorm_fwd", _dt(x), IN_D2S2, _p(x), None, None, 1, None, _p(w), _p(b),
-              _p(y), _p(mean), _p(rstd), rows, c, H, W, 0, eps, _s(x))
-    return y, mean, rstd
-
-
-def _d2s_ln_fake(x, w, b, eps):
-    B, H, W, C4 = x.shape
-    rows = B * 4 * H * W
-    return (x.new_empty(B, 4 * H * W, C4 // 4), x.new_empty(rows, dtype=torch.float32),
-            x.new_empty(rows, dtype=torch.float32))
-
-
-def _d2s_ln_backward(ctx, dy, _dm, _dr):
-    x, w, mean, rstd = ctx.saved_tensors
-    if dy is None:
-        return None, None, None, None
-    B, H, W, C4 = x.shape
-    c = C4 // 4
-    rows = B * 4 * H * W
-    dy = _as(dy, x.dtype)
-    dx = torch.empty_like(x)
-    dw, db, acc, direct = _ln_grads(ctx, c, x.device)
-    n, part = _ln_parts(rows, c, x.device)
-    _lib.call("msu_layernorm_bwd", _dt(x), IN_D2S2, _p(dy), _p(x), None, _p(w), _p(mean), _p(rstd),
-              _p(dx), None, None, 1, _p(part), n, _p(dw), _p(db), rows, c, H, W, 0, acc, _s(x))
-    if direct:
-        _ln_finish(ctx, part, n, c)
-        return dx, None, None, None
-    return dx, dw, db, None
-
-
-_d2s_layer_norm = _define("d2s_layer_norm",
-                          "(Tensor x, Tensor weight, Tensor bias, float eps) -> (Tensor, Tensor, Tensor)",
-                          _d2s_ln_impl, _d2s_ln_fake, _ln_setup, _d2s_ln_backward)
 
 
 def d2s_layer_norm(x, weight, bias, eps=1e-5):

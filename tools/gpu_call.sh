@@ -180,28 +180,18 @@ for s in "$@"; do
         MSU_LIB_OVERRIDE=$L timeout -k 10 200 python -u $R/tools/mlp_s1_one.py ${S1_C:-192} ${S1_M:-131072} 20 2>&1 | grep fused >> $O/${TAG}_mlp_s1_var.log || exit 3
       done; done
       cat $O/${TAG}_mlp_s1_var.log ;;
-    ln_exp)
-      for X in ${LN_EXP:-0 1 2 8}; do
-        L=""; [ $X != 0 ] && L=$R/tools/exp/libmsunet_layernorm_$X.so
-        echo "== MSU_EXP=$X" >> $O/${TAG}_ln_exp.log
-        for K in ln lnadd; do
-          MSU_LIB_OVERRIDE=$L timeout -k 10 200 python -u $R/tools/kbench.py $K >> $O/${TAG}_ln_exp.log 2>&1 || exit 3
+    ln_kern)
+      # LayerNorm kernel times at the step's shapes (plain and add mode, forward and backward), an
+      # override library (AB_LIB, label B1..B3) against this build (A1..A3), interleaved B A B A B A
+      for i in 1 2 3; do
+        for L in "$AB_LIB" ""; do
+          lab=A; [ -n "$L" ] && lab=B
+          d=$O/${TAG}_lnk_$lab$i
+          MSU_LIB_OVERRIDE=$L timeout -s KILL 120 rocprofv3 --kernel-trace --stats -d $d -o p --output-format csv -- python3 $R/tools/ln_one.py 5 > /dev/null 2>&1 || exit 3
+          python3 $R/tools/kstats.py $d/p_kernel_stats.csv ln_ $lab$i >> $O/${TAG}_ln_kern.log
         done
       done
-      cat $O/${TAG}_ln_exp.log ;;
-    ln_kern)
-      # LayerNorm kernel times at the step's shapes per ablation build (LN_EXP masks, 0 = this build)
-      for X in ${LN_EXP:-0 16 32 64}; do
-        L=""; [ $X != 0 ] && L=$R/tools/exp/libmsunet_layernorm_$X.so
-        d=$O/${TAG}_lnk_$X
-        MSU_LIB_OVERRIDE=$L timeout -s KILL 120 rocprofv3 --kernel-trace --stats -d $d -o p --output-format csv -- python3 $R/tools/ln_one.py 5 > /dev/null 2>&1 || exit 3
-        python3 $R/tools/kstats.py $d/p_kernel_stats.csv ln_ X$X >> $O/${TAG}_ln_kern.log
-      done
       cat $O/${TAG}_ln_kern.log ;;
-    ab_ln) bash $R/tools/gpu_bench_ab.sh ${TAG}_ln "" "MSU_LIB_OVERRIDE=$R/tools/exp/libmsunet_layernorm_1.so" \
-             "MSU_LIB_OVERRIDE=$R/tools/exp/libmsunet_layernorm_2.so" "MSU_LIB_OVERRIDE=$R/tools/exp/libmsunet_layernorm_8.so" \
-             "" "MSU_LIB_OVERRIDE=$R/tools/exp/libmsunet_layernorm_1.so" "MSU_LIB_OVERRIDE=$R/tools/exp/libmsunet_layernorm_2.so" \
-             "MSU_LIB_OVERRIDE=$R/tools/exp/libmsunet_layernorm_8.so" || exit 3 ;;
     nt_store) step nt_store 400 bash $R/tools/nt_store_ab.sh ;;
     ab_lib) bash $R/tools/gpu_bench_ab.sh ${TAG}_lib "" "MSU_LIB_OVERRIDE=$AB_LIB" "" "MSU_LIB_OVERRIDE=$AB_LIB" "" "MSU_LIB_OVERRIDE=$AB_LIB" || exit 3 ;;
     tail_tests) step tail_tests 600 $PYT -m gpu $R/tests/test_gpu_tail_reduce.py $R/tests/test_gpu_ln_side.py \
