@@ -412,6 +412,30 @@ int msu_loss_scale_step(double* hyper, const float* found_inf, float* scale, int
  * (GradScaler's non-finite check, torch._amp_foreach_non_finite_check_and_unscale_). */
 int msu_nonfinite(const float* x, long n, float* flag, void* stream);
 int msu_nonfinite2(const float* x0, long n0, const float* x1, long n1, float* flag, void* stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) inside the device-side step.
+ * msu_grad_sumsq2 is msu_nonfinite2 that also sums: part[b] = the sum, in f64 and in a fixed
+ * order, of (double)x * (double)x over workgroup b's share of [x0 | x1] (the square of an f32 is
+ * exact in f64: nothing under- or overflows), all nblk = msu_grad_sumsq_nblk(n0 + n1) partials
+ * written (0 for a workgroup without elements: part needs no clearing), no atomics, bitwise
+ * reproducible.  flag[0] = 1 if any element is inf/NaN, untouched otherwise (msu_nonfinite2's
+ * contract; flag may be null).  Any n0, n1 >= 0 (x1 null with n1 == 0) and any 4-byte-aligned
+ * pointers: 16-byte loads between each buffer's own scalar head and tail.  msu_grad_sumsq_nblk
+ * depends on n alone (1 <= nblk <= 1024), not on the device.  -2, nothing launched: part null,
+ * x null with n > 0, n < 0, nblk != msu_grad_sumsq_nblk(n0 + n1). */
+int msu_grad_sumsq_nblk(long n);
+int msu_grad_sumsq2(const float* x0, long n0, const float* x1, long n1, double* part, int nblk, float* flag,
+                    void* stream);
+/* One workgroup, every step one IEEE double operation, each output rounded to f32 once:
+ *   S = fixed-order sum of part[0:nblk];  inv = inv_in ? inv_in[0] : 1;  norm = sqrt(S) * inv;
+ *   coef = max_norm / (norm + 1e-6);  norm_out[0] = norm;  inv_out[0] = inv * (coef < 1 ? coef : 1)
+ * inv_in: the factor msu_adamw_dev2 would have unscaled by (null, 1 / world or msu_loss_scale_step's
+ * inv_out); inv_out takes its place, so AdamW consumes the clipped gradient with no extra pass,
+ * and norm is the norm of exactly what AdamW consumes.  A NaN coef (a non-finite step, skipped
+ * anyway) leaves inv as it is.  max_norm > 0; +inf measures and never clips.  -2, nothing
+ * launched: part / norm_out / inv_out null, nblk outside [1, 1024], max_norm <= 0 or NaN,
+ * inv_out aliasing inv_in or norm_out. */
+int msu_grad_clip_scale(const double* part, int nblk, const float* inv_in, double max_norm, float* norm_out,
+                        float* inv_out, void* stream);
 int msu_cast(int dtype, const float* x, void* y, long n, void* stream);
 /* The refine conv's f32 weight W [Cout][Cin][3][3] (model_parts.py:447-448) in the conv kernels'
  * layouts, in the activation dtype: flip 0 -> Wt of msu_conv3x3_fwd/_fwd2 [9][Cout][roundup(Cin,32)];

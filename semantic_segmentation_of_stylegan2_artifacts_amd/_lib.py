@@ -60,6 +60,9 @@ SIGNATURES = {
     "msu_adamw": (I, [P, P, P, P, L, F, F, F, F, F, I, P, P, P]),
     "msu_nonfinite": (I, [P, L, P, P]),
     "msu_nonfinite2": (I, [P, L, P, L, P, P]),
+    "msu_grad_sumsq_nblk": (I, [L]),
+    "msu_grad_sumsq2": (I, [P, L, P, L, P, I, P, P]),
+    "msu_grad_clip_scale": (I, [P, I, P, D, P, P, P]),
     "msu_adamw_dev": (I, [P, P, P, P, L, P, D, D, D, D, P, P, P]),
     "msu_adamw_dev2": (I, [P, P, P, P, L, P, D, D, D, D, P, P, P, I, I, P]),
     "msu_step_advance": (I, [P, P, P]),

@@ -2108,6 +2108,48 @@ def nonfinite_(x, flag, x2=None):
         _lib.call("msu_nonfinite2", _p(x), x.numel(), _p(x2), x2.numel(), _p(flag), _s(x))
 
 
+def grad_sumsq_blocks(n):
+    """Partial sums grad_sumsq_ writes for n elements (a function of n alone, 1..1024)."""
+    return _lib.lib().msu_grad_sumsq_nblk(int(n))
+
+
+def grad_sumsq_(x, part, flag, x2=None):
+    """nonfinite_ that also sums: part (f64 [grad_sumsq_blocks(n)]) receives fixed-order f64
+    partial sums of x^2 over [x | x2] (every entry written, no atomics, bitwise reproducible);
+    flag[0] = 1 if an element is inf / NaN, untouched otherwise (flag may be None)."""
+    _need_cuda(x, part, flag, x2)
+    n = x.numel() + (x2.numel() if x2 is not None else 0)
+    if x.dtype != torch.float32 or (x2 is not None and x2.dtype != torch.float32) or not x.is_contiguous() \
+            or (x2 is not None and not x2.is_contiguous()):
+        raise ValueError("grad_sumsq_: x / x2 must be contiguous f32 buffers")
+    if part.dtype != torch.float64 or not part.is_contiguous() or part.numel() != grad_sumsq_blocks(n):
+        raise ValueError(f"grad_sumsq_: part must be f64 [{grad_sumsq_blocks(n)}] for {n} elements")
+    if flag is not None and (flag.dtype != torch.float32 or flag.numel() < 1):
+        raise ValueError("grad_sumsq_: flag f32 [1]")
+    _lib.call("msu_grad_sumsq2", _p(x), x.numel(), _p(x2), x2.numel() if x2 is not None else 0, _p(part),
+              part.numel(), _p(flag), _s(x))
+
+
+def grad_clip_scale_(part, inv_in, max_norm, norm_out, inv_out):
+    """clip_grad_norm_'s rule on the factor AdamW unscales by, one launch: norm_out = sqrt(sum of
+    part) * inv and inv_out = inv * min(1, max_norm / (norm + 1e-6)), with inv = inv_in[0] (None:
+    1), the factor adamw_dev_ would have received; inv_out takes its place.  max_norm > 0,
+    float("inf") measures without clipping.  norm_out / inv_out f32 [1], trainer.grad_clip_rule
+    restates it on the host."""
+    _need_cuda(part, inv_in, norm_out, inv_out)
+    if part.dtype != torch.float64 or not part.is_contiguous() or not 1 <= part.numel() <= 1024:
+        raise ValueError("grad_clip_scale_: part must be f64 [1..1024] (grad_sumsq_'s partial sums)")
+    if norm_out.dtype != torch.float32 or inv_out.dtype != torch.float32 or norm_out.numel() < 1 \
+            or inv_out.numel() < 1 or (inv_in is not None and (inv_in.dtype != torch.float32 or inv_in.numel() < 1)):
+        raise ValueError("grad_clip_scale_: inv_in / norm_out / inv_out f32 [1]")
+    if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not max_norm > 0:
+        raise ValueError(f"grad_clip_scale_: max_norm must be a number > 0 (inf allowed), got {max_norm!r}")
+    if inv_out.data_ptr() in (norm_out.data_ptr(), _p(inv_in)):
+        raise ValueError("grad_clip_scale_: inv_out must not alias inv_in or norm_out")
+    _lib.call("msu_grad_clip_scale", _p(part), part.numel(), _p(inv_in), float(max_norm), _p(norm_out),
+              _p(inv_out), _s(part))
+
+
 def adamw_dev_(param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2, eps, weight_decay, inv_scale=None,
                found_inf=None, shadow=None, zero_grad=False):
     """AdamW over flat f32 buffers with lr and step read from the device tensor

@@ -325,6 +325,21 @@ def loss_scale_rule(scale, tracker, found_inf, growth=2.0, backoff=0.5, interval
     return (grown if math.isfinite(grown) else scale), 0
 
 
+def grad_clip_rule(sumsq, inv, max_norm):
+    """Host restatement of ``msu_grad_clip_scale`` (``torch.nn.utils.clip_grad_norm_`` on the
+    factor AdamW unscales by): (norm, factor) from the f64 sum of squares of the raw gradients,
+    the factor AdamW would have multiplied them by (``inv``; None = 1) and ``max_norm``.  Python
+    floats are doubles: every step is one IEEE double operation, each result rounds to f32 once.
+    A NaN coefficient (a non-finite sum: the step is skipped anyway) leaves the factor at inv."""
+    def f32(v):
+        return torch.tensor(v, dtype=torch.float64).to(torch.float32).item()
+    sumsq = float(sumsq)
+    inv = 1.0 if inv is None else float(inv)
+    norm = math.sqrt(sumsq) * inv
+    coef = float(max_norm) / (norm + 1e-6)
+    return f32(norm), f32(inv * (coef if coef < 1.0 else 1.0))
+
+
 def reseed(seed, rank=0):
     """Per-rank randomness for data parallelism: the model is built from the shared seed
     (identical initial weights on every rank), then every rank draws its own drop-path and
@@ -361,7 +376,7 @@ class Trainer:
     def __init__(self, model, config, device, lr=None, amp_dtype=torch.bfloat16, bucket_mb=32,
                  world_size=1, process_group=None, rank=0, seed=None, skip_nonfinite=True, use_graph=None,
                  graph_warmup=4, grad_wire_dtype=None, always_reduce=False, loss_scale=None, init_scale=65536.0,
-                 growth_interval=2000):
+                 growth_interval=2000, max_grad_norm=None):
         self.model = model
         self.device = device
         self.amp_dtype = amp_dtype
@@ -385,6 +400,12 @@ class Trainer:
                 raise ValueError(f"loss scale {start} / growth_interval {growth_interval}: need a finite "
                                  "positive scale and an interval >= 1")
         self.growth_interval = int(growth_interval)
+        # max_grad_norm: None (no clipping, nothing allocated or launched), a positive float
+        # (clip_grad_norm_ on the averaged, unscaled gradient of both groups) or float("inf") (the
+        # norm readout alone).  A non-finite norm must skip the step, not scale it by NaN
+        self._max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        if max_grad_norm is not None and not skip_nonfinite:
+            raise ValueError("max_grad_norm needs skip_nonfinite=True: a step with a non-finite norm must be skipped")
         if seed is not None:
             reseed(seed, rank)
         core = model.ms_unet if hasattr(model, "ms_unet") else model
@@ -434,6 +455,15 @@ class Trainer:
         t = config.TRAIN
         self.loss_fn = DynamicLoss(alpha=t.TVERSKY_LOSS_ALPHA, beta=t.TVERSKY_LOSS_BETA,
                                    tversky_bce_mix=t.LOSS_TVERSKY_BCE_MIX)
+        # clipping's persistent buffers (allocated once: the step stays capturable): the partial
+        # sums of squares, the last step's gradient norm and the factor AdamW receives
+        self.part = self.grad_norm_dev = self.clip_inv = None
+        if max_grad_norm is not None:
+            n = sum(g.grad.numel() for g in self.groups)
+            nblk = ops.grad_sumsq_blocks(n) if torch.device(device).type == "cuda" else 1
+            self.part = torch.zeros(nblk, device=device, dtype=torch.float64)
+            self.grad_norm_dev = torch.zeros(1, device=device, dtype=torch.float32)
+            self.clip_inv = torch.ones(1, device=device, dtype=torch.float32)
         self.world_size = world_size
         self.step_count = 0
         self._applied_base = 0  # AdamW step count not taken by this trainer (loaded checkpoints)
@@ -484,6 +514,35 @@ class Trainer:
     def lr(self, value):
         self._lr = float(value)
         self.hyper[0:1].fill_(self._lr)
+
+    @staticmethod
+    def _check_max_grad_norm(value):
+        if value is None:
+            return None
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not value > 0:
+            raise ValueError(f"max_grad_norm must be None or a number > 0 (float('inf'): measure only), got {value!r}")
+        return float(value)
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        """A launch argument of the captured step: the graph is dropped when it changes.  The
+        feature itself (its buffers, the skip rule) is chosen at construction."""
+        value = self._check_max_grad_norm(value)
+        if (value is None) != (self._max_grad_norm is None):
+            raise ValueError("gradient clipping is switched on or off at construction (max_grad_norm=...)")
+        if value != self._max_grad_norm:
+            self.invalidate_graph()
+        self._max_grad_norm = value
+
+    def grad_norm(self):
+        """The last step's global gradient norm, of exactly what AdamW consumed (reduced,
+        averaged over ranks, unscaled; non-finite on a skipped step); None without
+        max_grad_norm; syncs.  ``grad_norm_dev`` is the device tensor, for logging without a sync."""
+        return None if self.grad_norm_dev is None else float(self.grad_norm_dev.item())
 
     def optimizer_steps(self):
         """AdamW steps actually applied (skipped non-finite steps excluded); syncs."""
@@ -663,7 +722,10 @@ class Trainer:
             found = self.found_inf
             if not self._flag_reset_by_loss:
                 found.zero_()
-            ops.nonfinite_(self.groups[0].grad, found, self.groups[1].grad)
+            if self._max_grad_norm is None:
+                ops.nonfinite_(self.groups[0].grad, found, self.groups[1].grad)
+            else:  # the same single read, summing the squares as it checks
+                ops.grad_sumsq_(self.groups[0].grad, self.part, found, self.groups[1].grad)
             if wire_scaled:
                 self.reducer.update_scale(found)
         if self.scale is None:
@@ -674,6 +736,11 @@ class Trainer:
             ops.loss_scale_step_(self.hyper, found, self.scale, self.growth_tracker, self.inv_out, inv,
                                  self.scale_factors[0], self.scale_factors[1], self.growth_interval)
             inv = self.inv_out
+        if self._max_grad_norm is not None:
+            # one workgroup: the norm of what AdamW is about to consume, and the clip coefficient
+            # folded into the factor it multiplies every gradient by (no extra pass over them)
+            ops.grad_clip_scale_(self.part, inv, self._max_grad_norm, self.grad_norm_dev, self.clip_inv)
+            inv = self.clip_inv
         for g in self.groups:
             # the gradient reset and (16-bit) the shadow refresh ride in AdamW's pass: no fill and
             # no re-read of the parameters for the cast (a skipped step leaves the shadow as is
