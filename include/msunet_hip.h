@@ -253,6 +253,11 @@ int msu_tok_gemm_supported_epi(long M, int N, int K, int epi);
 int msu_tok_gemm(int dtype, const void* A, const void* A2, int K1, const void* W, const float* bias, void* Y,
                  void* Y2, const void* H, long M, int N, int K, int epi, void* stream);
 int msu_tok_gemm_plan(long M, int N, int K, long* out6);
+/* Host only: out6 = {kc, nc, nst * 100 + nw, nchunk, grid, lds bytes} of the plan msu_tok_gemm
+ * launches for epilogue epi (concat != 0: with the split-A input); -3 and nc = 0 where it has none
+ * (the 48-deep stage, K % 48 == 0 with K a multiple of neither 96 nor 128, serves the plain
+ * epilogue without split A only).  msu_tok_gemm_plan is the plain epilogue's. */
+int msu_tok_gemm_plan_epi(long M, int N, int K, int epi, int concat, long* out6);
 /* Persistent tiled NT GEMM (128 x 128 tiles, LDS-DMA double buffering, one flat K-step sequence per
  * workgroup) for the stage 1-3 Linears, whose wide weights do not fit the token GEMM's LDS: same
  * Y / epi semantics as msu_tok_gemm.  Covered: N % 32 == 0, K % 64 == 0. */
@@ -260,6 +265,11 @@ int msu_nt_gemm_supported(long M, int N, int K);
 /* Tile msu_nt_gemm picks for an M x N output (rows * 1000 + columns; 128/256 x 128/192/256),
  * + 1000000 when the ping-pong kernel (gemm_pp.h) takes it. */
 int msu_nt_gemm_plan(long M, int N);
+/* Host only: what msu_nt_gemm (wkn = 0) / msu_nt_gemm_kn (wkn != 0) launch for (M, N, K, epi)
+ * under the mode bits in force: out8 = {tile rows, tile columns, ring form (2 two-stage, 3
+ * three-stage, 4 A3W2), ping-pong kernel, tiles, grid, tile queue used, CU count}; -2 where the
+ * shape is not covered. */
+int msu_nt_gemm_plan2(long M, int N, int K, int epi, int wkn, long* out8);
 /* bit 0: the ping-pong kernel where the shape tiles exactly (default off: the persistent
  * 2-barrier kernel everywhere; A/B switch MSU_NT_PP); bits 1-2: a forced tile form (timing
  * tools); bit 3: the 256 x 192 A3W2 ring; bit 4: the two-stage kernel claims its tiles from a

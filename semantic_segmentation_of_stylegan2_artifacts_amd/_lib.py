@@ -89,8 +89,10 @@ SIGNATURES = {
     "msu_tok_gemm_supported_epi": (I, [L, I, I, I]),
     "msu_tok_gemm": (I, [I, P, P, I, P, P, P, P, P, L, I, I, I, P]),
     "msu_tok_gemm_plan": (I, [L, I, I, P]),
+    "msu_tok_gemm_plan_epi": (I, [L, I, I, I, I, P]),
     "msu_nt_gemm_supported": (I, [L, I, I]),
     "msu_nt_gemm_plan": (I, [L, I]),
+    "msu_nt_gemm_plan2": (I, [L, I, I, I, I, P]),
     "msu_nt_gemm_mode": (I, [I]),
     "msu_nt_gemm": (I, [I, P, P, P, P, P, P, L, I, I, I, P]),
     "msu_nt_gemm_kn": (I, [I, P, P, P, P, P, P, L, I, I, I, P]),

@@ -542,14 +542,49 @@ NtCfg nt_cfg(long M, int N, bool wkn) {
   return best;
 }
 
+// What a launch of (M, N, K, epi, weight form) runs under the mode bits in force: tile rows (64 wm)
+// and columns, ring form (2, 3, or 4 = A3W2), ping-pong kernel or gemm_nt_kernel, tile counts, grid
+// and whether the two-stage kernel claims its tiles from the queue.  nt_launch launches exactly
+// this; msu_nt_gemm_plan2 reports it.
+struct NtPlan {
+  int wm, bn, nst;
+  bool pp, queue;
+  int tiles_m, tiles_n;
+  long tiles;
+  unsigned grid;
+};
+
+NtPlan nt_plan(long M, int N, int K, int epi, bool wkn) {
+  NtPlan p;
+  const long cus = msu_num_cus();
+  const int pbn = pp_bn(M, N, K, epi, wkn);
+  if (pbn) {
+    p.wm = pp::BM / 64; p.bn = pbn; p.nst = 2; p.pp = true; p.queue = false;
+    p.tiles_n = N / pbn;
+    p.tiles_m = (int)(M / pp::BM);
+    p.tiles = (long)p.tiles_m * p.tiles_n;
+    p.grid = (unsigned)(p.tiles < cus ? p.tiles : cus);
+    return p;
+  }
+  const NtCfg cfg = nt_cfg(M, N, wkn);
+  p.wm = cfg.wm; p.bn = cfg.bn; p.pp = false;
+  p.nst = cfg.bn == 192 ? (cfg.wm == 4 && g_nt_a3 ? 4 : 2) : (cfg.wm == 4 ? 3 : 2);
+  p.tiles_n = (N + cfg.bn - 1) / cfg.bn;
+  p.tiles_m = (int)((M + 64 * cfg.wm - 1) / (64 * cfg.wm));
+  p.tiles = (long)((M + 64 * cfg.wm - 1) / (64 * cfg.wm)) * p.tiles_n;
+  const long cap = cus * (cfg.wm == 2 ? 2 : 1);
+  p.grid = (unsigned)(p.tiles < cap ? p.tiles : cap);
+  p.queue = p.nst == 2 && g_nt_dyn && K >= 2 * BK;
+  return p;
+}
+
 template <typename T, int WM, int NST, bool WKN, int BNT, int KB = 64>
-void launch_nt(int epi, const NtArgs& a, hipStream_t st) {
-  const long tiles = (long)a.tiles_m * a.tiles_n;
-  const long cap = (long)msu_num_cus() * (WM == 2 ? 2 : 1);
-  const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
+void launch_nt(int epi, const NtPlan& p, const NtArgs& a, hipStream_t st) {
+  static_assert(KB == BK, "nt_plan's queue rule is in K steps of BK");
+  const unsigned grid = p.grid;
   const dim3 blk(128 * WM);
   NtArgs q = a;
-  q.tq = NST == 2 && g_nt_dyn && a.K >= 2 * KB ? tile_queue(st) : nullptr;
+  q.tq = p.queue ? tile_queue(st) : nullptr;
   switch (epi) {
     case EPI_PLAIN: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_PLAIN, WM, NST, WKN, BNT, KB>), dim3(grid), blk, 0, st, q); break;
     case EPI_GELU_DUAL: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_GELU_DUAL, WM, NST, WKN, BNT, KB>), dim3(grid), blk, 0, st, q); break;
@@ -578,33 +613,28 @@ int nt_launch(int dtype, const void* A, const void* W, const float* bias, void* 
   a.M = (int)M;
   a.N = N;
   a.K = K;
-  const NtCfg cfg = nt_cfg(M, N, wkn);
-  a.tiles_n = (N + cfg.bn - 1) / cfg.bn;
-  a.tiles_m = (int)((M + 64 * cfg.wm - 1) / (64 * cfg.wm));
-  if ((long)a.tiles_m * a.tiles_n >= (1L << 31)) return -2;
+  const NtPlan p = nt_plan(M, N, K, epi, wkn);
+  if (p.tiles >= (1L << 31)) return -2;
+  a.tiles_n = p.tiles_n;
+  a.tiles_m = p.tiles_m;
   hipStream_t st = (hipStream_t)stream;
-  const int pbn = pp_bn(M, N, K, epi, wkn);
-  if (pbn) {
-    a.tiles_n = N / pbn;
-    a.tiles_m = (int)(M / pp::BM);
-    const long tiles = (long)a.tiles_m * a.tiles_n;
-    const unsigned grid = (unsigned)(tiles < msu_num_cus() ? tiles : msu_num_cus());
+  if (p.pp) {
     MSU_DISPATCH16(dtype, T,
-      if (epi == EPI_PLAIN) hipLaunchKernelGGL((pp::gemm_pp_kernel<T, EPI_PLAIN, 192>), dim3(grid), dim3(512), 0, st, a);
-      else hipLaunchKernelGGL((pp::gemm_pp_kernel<T, EPI_GELU_DUAL, 192>), dim3(grid), dim3(512), 0, st, a));
+      if (epi == EPI_PLAIN) hipLaunchKernelGGL((pp::gemm_pp_kernel<T, EPI_PLAIN, 192>), dim3(p.grid), dim3(512), 0, st, a);
+      else hipLaunchKernelGGL((pp::gemm_pp_kernel<T, EPI_GELU_DUAL, 192>), dim3(p.grid), dim3(512), 0, st, a));
     return MSU_CHECK_LAUNCH();
   }
   MSU_DISPATCH16(dtype, T,
-    if (cfg.bn == 192) {
-      if (cfg.wm == 4 && g_nt_a3) launch_nt<T, 4, 4, false, 192>(epi, a, st);
-      else if (cfg.wm == 4) launch_nt<T, 4, 2, false, 192>(epi, a, st);
-      else launch_nt<T, 2, 2, false, 192>(epi, a, st);
-    } else if (cfg.wm == 4) {
-      if (wkn) launch_nt<T, 4, 3, true, 128>(epi, a, st);
-      else launch_nt<T, 4, 3, false, 128>(epi, a, st);
+    if (p.bn == 192) {
+      if (p.nst == 4) launch_nt<T, 4, 4, false, 192>(epi, p, a, st);
+      else if (p.wm == 4) launch_nt<T, 4, 2, false, 192>(epi, p, a, st);
+      else launch_nt<T, 2, 2, false, 192>(epi, p, a, st);
+    } else if (p.wm == 4) {
+      if (wkn) launch_nt<T, 4, 3, true, 128>(epi, p, a, st);
+      else launch_nt<T, 4, 3, false, 128>(epi, p, a, st);
     } else {
-      if (wkn) launch_nt<T, 2, 2, true, 128>(epi, a, st);
-      else launch_nt<T, 2, 2, false, 128>(epi, a, st);
+      if (wkn) launch_nt<T, 2, 2, true, 128>(epi, p, a, st);
+      else launch_nt<T, 2, 2, false, 128>(epi, p, a, st);
     });
   return MSU_CHECK_LAUNCH();
 }
@@ -630,10 +660,21 @@ int msu_nt_gemm_supported(long M, int N, int K) { return nt_shape_ok(M, N, K) ? 
 // The tile msu_nt_gemm picks for M x N (the [N, K] weight form, plain epilogue, K = 384):
 // rows * 1000 + columns, + 1000000 for the ping-pong kernel.
 int msu_nt_gemm_plan(long M, int N) {
-  const int pbn = pp_bn(M, N, 384, EPI_PLAIN, false);
-  if (pbn) return 1000000 + pp::BM * 1000 + pbn;
-  const NtCfg c = nt_cfg(M, N, false);
-  return 64 * c.wm * 1000 + c.bn;
+  const NtPlan p = nt_plan(M, N, 384, EPI_PLAIN, false);
+  return (p.pp ? 1000000 : 0) + 64 * p.wm * 1000 + p.bn;
+}
+
+// Host only: what msu_nt_gemm (wkn = 0) / msu_nt_gemm_kn (wkn != 0) launch for this shape and
+// epilogue under the mode bits in force (nt_plan): out8 = {tile rows, tile columns, ring form (2:
+// two-stage, 3: three-stage, 4: A3W2), ping-pong kernel, tiles, grid, tile queue used, CU count}.
+// -2 where the shape is not covered.
+int msu_nt_gemm_plan2(long M, int N, int K, int epi, int wkn, long* out8) {
+  for (int i = 0; i < 8; ++i) out8[i] = 0;
+  if (!nt_shape_ok(M, N, K) || epi < 0 || epi > 2) return -2;
+  const NtPlan p = nt_plan(M, N, K, epi, wkn != 0);
+  out8[0] = 64 * p.wm; out8[1] = p.bn; out8[2] = p.nst; out8[3] = p.pp; out8[4] = p.tiles; out8[5] = p.grid;
+  out8[6] = p.queue; out8[7] = msu_num_cus();
+  return 0;
 }
 
 // bit 0 -- 1: the ping-pong kernel where the shape tiles exactly, 0 (the default, MSU_NT_PP=0): the

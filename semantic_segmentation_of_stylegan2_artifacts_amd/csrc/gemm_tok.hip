@@ -6,15 +6,23 @@
 namespace msu_tok {
 namespace {
 
-// Stage depth: the largest instantiated one dividing K.  Chunk width: the widest
-// instantiated multiple of 32 dividing N whose W image fits in LDS next to a 3-deep ring
-// (else a 2-deep one when that halves the chunk count).
-TokPlan tok_plan(long M, int N, int K, int epi = EPI_PLAIN) {
-  TokPlan p;
+// Stage depth: the largest instantiated one dividing K (0: none).
+int tok_kc(int K) {
   static const int kcs[] = {96, 128, 48};
   for (int kc : kcs)
-    if (K % kc == 0) { p.kc = kc; break; }
+    if (K % kc == 0) return kc;
+  return 0;
+}
+
+// Chunk width: the widest instantiated multiple of 32 dividing N whose W image fits in LDS next
+// to a 3-deep ring (else a 2-deep one when that halves the chunk count).  The 48-deep stage is
+// instantiated for the plain epilogue only (gemm_tok_k48.hip: dispatch_nc<T, 48, FULL = false>):
+// a GELU epilogue or the split-A input has no plan there.
+TokPlan tok_plan(long M, int N, int K, int epi = EPI_PLAIN, bool concat = false) {
+  TokPlan p;
+  p.kc = tok_kc(K);
   if (!p.kc) return p;
+  if (p.kc == 48 && (epi != EPI_PLAIN || concat)) return p;
   static const int ncs[] = {384, 288, 256, 192, 128, 96, 64};
   int best[2] = {0, 0};
   for (int i = 0; i < 2; ++i) {
@@ -80,11 +88,12 @@ int msu_tok_gemm(int dtype, const void* A, const void* A2, int K1, const void* W
   if (M < 0 || N % 32 || K % 16) return -2;
   if (M == 0) return 0;
   if (A2 != nullptr && (K1 <= 0 || K1 >= K || K1 % 8)) return -2;
+  if (A2 != nullptr && tok_kc(K) == 48) return -2;  // the 48-deep stage has no split-A form
   if (epi == EPI_GELU_DUAL && (Y2 == nullptr || bias == nullptr || A2 != nullptr)) return -3;
   if (epi == EPI_GELU_GRAD && (H == nullptr || bias != nullptr || A2 != nullptr)) return -3;
   if (epi == EPI_PLAIN && A2 != nullptr && bias == nullptr) return -3;
   if (epi < 0 || epi > 2) return -3;
-  const TokPlan p = tok_plan(M, N, K, epi);
+  const TokPlan p = tok_plan(M, N, K, epi, A2 != nullptr);
   if (!p.nc) return -3;
   TokArgs a;
   a.A = (const bf16_t*)A;
@@ -112,12 +121,17 @@ int msu_tok_gemm(int dtype, const void* A, const void* A2, int K1, const void* W
   return MSU_CHECK_LAUNCH();
 }
 
-// Plan introspection for tests / benchmarks: out6 = {kc, nc, nst, nchunk, grid, lds bytes}.
-int msu_tok_gemm_plan(long M, int N, int K, long* out6) {
-  const TokPlan p = tok_plan(M, N, K);
+// Plan introspection for tests / benchmarks (host only): out6 = {kc, nc, nst * 100 + nw, nchunk,
+// grid, lds bytes} of the plan msu_tok_gemm launches for epilogue `epi`, with the split-A input
+// when concat != 0; -3 (and nc = 0) where it has none.  msu_tok_gemm_plan: the plain epilogue.
+int msu_tok_gemm_plan_epi(long M, int N, int K, int epi, int concat, long* out6) {
+  TokPlan p;
+  if (M > 0 && N % 32 == 0 && K % 16 == 0 && epi >= 0 && epi <= 2) p = tok_plan(M, N, K, epi, concat != 0);
   out6[0] = p.kc; out6[1] = p.nc; out6[2] = p.nst * 100 + p.nw; out6[3] = p.nchunk; out6[4] = p.grid;
   out6[5] = (long)p.lds;
   return p.nc ? 0 : -3;
 }
+
+int msu_tok_gemm_plan(long M, int N, int K, long* out6) { return msu_tok_gemm_plan_epi(M, N, K, EPI_PLAIN, 0, out6); }
 
 }  // extern "C"

@@ -937,6 +937,16 @@ def tok_supported_epi(M, N, K, epi):
     return r
 
 
+def tok_supported_cat(M, N, K):
+    """``tok_supported`` for the split-A input (plain epilogue; the 48-deep stage has no such form)."""
+    key = ("cat", int(M), int(N), int(K))
+    r = _tok_cache.get(key)
+    if r is None:
+        out = (ctypes.c_long * 6)()
+        r = _tok_cache[key] = _lib.lib().msu_tok_gemm_plan_epi(int(M), int(N), int(K), TOK_PLAIN, 1, out) == 0
+    return r
+
+
 def tok_gemm(a, w, bias=None, epi=TOK_PLAIN, h=None, a2=None, gelu_only=False):
     """16-bit Y = epi(A . W^T + bias) on the token GEMM kernel.  a: [..., K1] (+ a2: [..., K-K1]),
     w: [N, K] (a's dtype), bias: [N] f32.  Returns Y (and GELU(Y) for TOK_GELU_DUAL).
@@ -1277,7 +1287,7 @@ def nt_gemm_cat(x, skip, w, bias):
 def _cat_route(M, N, K, C1):
     """The GEMM that takes a skip fusion without the concatenated copy, or None."""
     r = gemm_route(M, N, K)
-    if r == "tok" and C1 % 8 == 0:
+    if r == "tok" and C1 % 8 == 0 and tok_supported_cat(M, N, K):
         return "tok"
     if r == "nt" and C1 % 64 == 0:
         return "nt"

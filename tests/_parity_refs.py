@@ -17,6 +17,9 @@
 * ``conv3x3_ref64`` / ``conv3x3_abs64`` / ``conv3x3_wgrad_ref64`` / ``conv3x3_wgrad_abs64`` /
   ``gelu64`` / ``gelu_grad64``: the refine-conv family in float64 with its condition terms
   (tests/test_gpu_conv_matrix.py judges every kernel of csrc/conv3x3.h against them).
+* ``gemm_ref64`` / ``gemm_abs64``: a . w^T + b in float64 and its condition term (with ``gelu64`` /
+  ``gelu_grad64``: what tests/test_gpu_gemm_matrix.py judges the token GEMM, the NT GEMM and the
+  one-pass Linear backward against).
 * ``ln_plain_ref`` / ``ln_add_ref`` / ``ln_merge_ref`` / ``ln_d2s2_ref`` / ``ln_head_ref``: the
   four input modes of csrc/layernorm.hip and its 1-channel head in float64 (the one exception to
   "fp32" above: tests/test_gpu_ln_matrix.py judges f32 kernels against them).
@@ -174,6 +177,21 @@ def conv3x3_wgrad_ref64(a, dz, dtype=torch.float64):
 def conv3x3_wgrad_abs64(a, dz):
     """sum_pixels |a| |dz| per weight element and sum_pixels |dz| per bias element."""
     return conv3x3_wgrad_ref64(a.double().abs(), dz.double().abs())
+
+
+# ----------------------------------------------------------------------------- GEMM family
+# fp64 references of csrc/gemm_tok.h, gemm_nt.hip, gemm_pp.h and gemm_linbwd.hip
+# (tests/test_gpu_gemm_matrix.py), evaluated on the operands' device on exactly the stored operands.
+def gemm_ref64(a, w, b=None, dtype=torch.float64):
+    """a [M, K] . w [N, K]^T (+ b [N]) -> [M, N] in float64.  dtype = float32 evaluates the same
+    matmul with the float64 operands cast to f32 (the figure the GEMM matrix derives kappa from)."""
+    y = torch.matmul(a.double().to(dtype), w.double().to(dtype).t())
+    return y if b is None else y + b.double().to(dtype)
+
+
+def gemm_abs64(a, w, b=None):
+    """The same over absolute values: the condition term sum |a| |w| + |b| of every output."""
+    return gemm_ref64(a.double().abs(), w.double().abs(), None if b is None else b.double().abs())
 
 
 # ----------------------------------------------------------------------------- LayerNorm family

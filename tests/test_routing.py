@@ -44,3 +44,21 @@ def test_lib_switch_still_reaches_the_library(monkeypatch):
     monkeypatch.setattr(ops, "_ROUTE_FORCE", "lib")
     monkeypatch.setattr(ops, "_tok_cache", {})
     assert ops.gemm_route(8 * 64 ** 2, 3 * 384, 384) == "lib"
+
+
+def test_the_48_deep_token_stage_takes_the_plain_epilogue_only(monkeypatch):
+    """gemm_tok_k48.hip is built for the plain epilogue without split A: at K % 48 == 0 with K a
+    multiple of neither 96 nor 128 the token GEMM still takes a plain Linear, while a GELU epilogue
+    and the skip fusion are routed elsewhere (they used to be promised here and refused at launch)."""
+    monkeypatch.setattr(ops, "_ROUTE_FORCE", "")
+    monkeypatch.setattr(ops, "_tok_cache", {})
+    M = 8 * 256 ** 2
+    for K in (48, 144, 240):
+        assert ops.tok_supported_epi(M, 96, K, ops.TOK_PLAIN)
+        assert not ops.tok_supported_epi(M, 96, K, ops.TOK_GELU_DUAL)
+        assert not ops.tok_supported_epi(M, 96, K, ops.TOK_GELU_GRAD)
+        assert not ops.tok_supported_cat(M, 96, K)
+        assert ops.gemm_route(M, 96, K) == "tok"
+        assert ops.gemm_route(M, 96, K, ops.TOK_GELU_DUAL) != "tok"
+        assert ops._cat_route(M, 96, K, K // 2) != "tok"
+    assert ops.tok_supported_cat(M, 96, 192) and ops._cat_route(M, 96, 192, 96) == "tok"
