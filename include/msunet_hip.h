@@ -266,14 +266,14 @@ int msu_nt_gemm_supported(long M, int N, int K);
  * + 1000000 when the ping-pong kernel (gemm_pp.h) takes it. */
 int msu_nt_gemm_plan(long M, int N);
 /* Host only: what msu_nt_gemm (wkn = 0) / msu_nt_gemm_kn (wkn != 0) launch for (M, N, K, epi)
- * under the mode bits in force: out8 = {tile rows, tile columns, ring form (2 two-stage, 3
- * three-stage, 4 A3W2), ping-pong kernel, tiles, grid, tile queue used, CU count}; -2 where the
+ * under the mode bits in force: out8 = {tile rows, tile columns, ring depth (2 two-stage, 3
+ * three-stage), ping-pong kernel, tiles, grid, 0 (once: tile queue used), CU count}; -2 where the
  * shape is not covered. */
 int msu_nt_gemm_plan2(long M, int N, int K, int epi, int wkn, long* out8);
 /* bit 0: the ping-pong kernel where the shape tiles exactly (default off: the persistent
  * 2-barrier kernel everywhere; A/B switch MSU_NT_PP); bits 1-2: a forced tile form (timing
- * tools); bit 3: the 256 x 192 A3W2 ring; bit 4: the two-stage kernel claims its tiles from a
- * per-XCD device queue (opt-in MSU_NT_DYN=1: measured slower).  Returns the previous mode. */
+ * tools and the tests that reach each form).  Bits 3 and 4 once selected the A3W2 ring and the
+ * tile queue, both removed: they are ignored and read back 0.  Returns the previous mode. */
 int msu_nt_gemm_mode(int mode);
 int msu_nt_gemm(int dtype, const void* A, const void* W, const float* bias, void* Y, void* Y2, const void* H,
                 long M, int N, int K, int epi, void* stream);

@@ -294,10 +294,11 @@ int msu_num_cus();
 // Persistent kernels beside the side stream: a workgroup takes its first
 // tile statically and claims the others from a device counter, so workgroups that get a CU late
 // (the side stream's weight-gradient kernels hold whole CUs) take fewer tiles instead of running
-// a fixed share past the others' end.  A slot = 8 claim counters (one per XCD, for kernels
-// that keep each XCD on its own tile range; others use counter 0) and a finished-workgroup
-// count, each on its own 128-B line; the launch's last workgroup resets the slot (no memset
-// launch; graph-replay safe).  One slot per stream and translation unit.
+// a fixed share past the others' end.  A slot = 8 claim counters (one per XCD, for a kernel
+// that keeps each XCD on its own tile range; the refine convs, today's only users, take
+// counter 0) and a finished-workgroup count, each on its own 128-B line; the launch's last
+// workgroup resets the slot (no memset launch; graph-replay safe).  One slot per stream and
+// translation unit.
 namespace {
 constexpr int TQ_SLOTS = 16, TQ_LINE = 32, TQ_DONE = 8 * TQ_LINE, TQ_INTS = 9 * TQ_LINE;
 __device__ int g_tile_queue[TQ_SLOTS * TQ_INTS];

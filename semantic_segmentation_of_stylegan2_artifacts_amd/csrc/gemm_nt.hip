@@ -5,7 +5,7 @@
 // (up to 3072 x 768) and the token counts small (8k-131k), so the work is MFMA-heavier and
 // tiled both ways here:
 //   * 128 x 128 output tile per 4-wave workgroup (waves 2 x 2, 64 x 64 each, four 32 x 32
-//     accumulators), K steps of 64 (or 32);
+//     accumulators; also 256 rows and / or 192 columns, see gemm_nt_kernel), K steps of 64;
 //   * A and W tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4), double-buffered: the
 //     next K step's tiles are in flight while this one's MFMAs run (raw s_barrier);
 //   * persistent: the workgroups walk their tiles as one flat sequence of K steps (the ring
@@ -29,14 +29,9 @@
 #include "common.h"
 #include "mfma_frag.h"
 
-// MSU_EXP: ablation bits for timing experiments only (tools/build_exp.sh); 0 in every real build
-#ifndef MSU_EXP
-#define MSU_EXP 0
-#endif
-
 namespace {
 
-constexpr int BN = 128, BK = 64;  // N tile and K step of the KN form
+constexpr int BN = 128, BK = 64;  // N tile of the KN form, K step of every form
 enum { EPI_PLAIN = 0, EPI_GELU_DUAL = 1, EPI_GELU_GRAD = 2 };
 
 struct NtArgs {
@@ -49,24 +44,21 @@ struct NtArgs {
   const bf16_t* H;     // [M][N] (GELU_GRAD: pre-activation)
   int M, N, K, K1;
   int tiles_m, tiles_n;
-  int* tq;             // tile-queue slot (common.h; the two-stage kernel only) or null: static
 };
 
-// A ROWS x KB operand tile (K-contiguous rows, KB = 64 or 32) staged by NTHR threads.  A 256-B
-// LDS bank row holds RPL = 128 / KB tile rows; chunk c of row r is stored at chunk c ^ ((r / RPL)
-// % CH), so a half-wave's 16 fragment rows (16 B each) land on 16 distinct bank groups.  When the
-// tile's 16-B slots are not a whole number of rounds of NTHR (192 rows x 4 chunks over 512
-// threads), the last round is issued by the first FULLW waves only (wave-uniform).
-template <int ROWS, int NTHR, int KB = 64>
+// A ROWS x BK operand tile (K-contiguous rows) staged by NTHR threads.  A 256-B LDS bank row holds
+// RPL = 2 tile rows; chunk c of row r is stored at chunk c ^ ((r / RPL) % CH), so a half-wave's
+// 16 fragment rows (16 B each) land on 16 distinct bank groups.  When the tile's 16-B slots are
+// not a whole number of rounds of NTHR, the last round is issued by the first FULLW waves only
+// (wave-uniform; every tile instantiated today is whole rounds, FULLW = all waves).
+template <int ROWS, int NTHR>
 struct RowTile {
-  static constexpr int CH = KB / 8, RPL = 128 / KB;
+  static constexpr int CH = BK / 8, RPL = 128 / BK;
   static constexpr int PER = (ROWS * CH + NTHR - 1) / NTHR;  // DMA instructions per thread (max)
   static constexpr int FULLW = (ROWS * CH - (PER - 1) * NTHR) / 64;  // waves issuing all PER
-  static_assert((ROWS * CH) % 64 == 0 && KB % 32 == 0, "whole-wave DMA instructions");
-  // DMA instructions of wave w
-  static MSU_DEV constexpr int per_wave(int w) { return w < FULLW ? PER : PER - 1; }
+  static_assert((ROWS * CH) % 64 == 0, "whole-wave DMA instructions");
   // LDS element offset of k-chunk `chunk` (8 elements) of tile row `row`
-  static MSU_DEV int off(int row, int chunk) { return row * KB + ((chunk ^ ((row / RPL) % CH)) << 3); }
+  static MSU_DEV int off(int row, int chunk) { return row * BK + ((chunk ^ ((row / RPL) % CH)) << 3); }
   // slot p = c * NTHR + tid is row p / CH, LDS chunk p % CH, which holds the global chunk that
   // off() puts there; rows past the tensor re-read its last row (their results are never stored)
   static MSU_DEV void stage(const bf16_t* __restrict__ src, int row0, int rows, int K, int k0, bf16_t* tile,
@@ -141,89 +133,55 @@ struct KnTile {
 // accumulators).  192 makes the N = 384 / 768 / 1152 / 2304 shapes of Swin-T's stages 2-3 whole
 // rounds of tiles on 256 CUs (N = 384 at M = 32768: 256 tiles of 256 x 192 instead of 384 of
 // 256 x 128, i.e. 1.5 rounds); KN (input-gradient) form: 128 only.
-// KB: K step (64).  A 32-deep step with a four-stage ring (three steps in flight in the same LDS)
-// was 25-50 % slower on every stage 1-3 shape (r04u) and is gone.
-// NST = 4 (A3W2): the 256 x 192 tile with the A operand two K steps ahead -- a ring of THREE A
-// stages (32 KB each) beside TWO W stages (24 KB): 144 KB, where three whole stages (168 KB) do not
-// fit.  A streams from HBM (or a sibling N tile's L2 lines), W is a small L2-resident weight: the
-// operand with the long latency gets the deeper prefetch.  Per step s the waves issue W(s + 1), then
-// A(s + 2); the wait for step s lets A(s + 1) (and a preceding epilogue's stores) stay in flight.
-template <typename T, int EPI, int WM, int NST, bool WKN, int BNT, int KB>
+// The K step is 64 (BK).  A 32-deep step with a four-stage ring (three steps in flight in the same
+// LDS) was 25-50 % slower on every stage 1-3 shape (r04u) and is gone; so are a
+// 256 x 192 tile with A two K steps ahead and a per-XCD tile queue for the two-stage forms (r06l,
+// r06q: both slower).
+template <typename T, int EPI, int WM, int NST, bool WKN, int BNT>
 __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
   constexpr int NTHR = 128 * WM, BM = 64 * WM, NI = BNT / 64;
-  constexpr bool A3 = NST == 4;
-  static_assert(!WKN || (BNT == BN && KB == BK), "KN tiles are 128 wide, 64 deep");
-  static_assert(!A3 || (!WKN && WM == 4 && BNT == 192), "A3W2: the 256 x 192 NT tile");
-  typedef RowTile<BM, NTHR, KB> TA;
-  typedef RowTile<BNT, NTHR, KB> TW;
+  static_assert(!WKN || BNT == BN, "KN tiles are 128 wide");
+  typedef RowTile<BM, NTHR> TA;
+  typedef RowTile<BNT, NTHR> TW;
   typedef KnTile<NTHR> TK;
-  constexpr int KSL = KB / 16;  // 16-wide k slices per step
-  constexpr int STG = (BM + BNT) * KB;  // elements per ring stage
+  constexpr int KSL = BK / 16;  // 16-wide k slices per step
+  constexpr int STG = (BM + BNT) * BK;  // elements per ring stage
   // per thread and step: DMA instructions (waves below DW0 issue D, the others D - 1), and
   // epilogue stores of a tile
   constexpr int D = TA::PER + (WKN ? TK::PER : TW::PER);
   static_assert(TA::FULLW * 64 == NTHR, "A rows: whole rounds");
   constexpr int DW0 = WKN ? 64 : TW::FULLW;
   constexpr int E = (EPI == EPI_GELU_DUAL ? 8 : 4) * NI;
-  static_assert(NST >= 2 && NST <= 4, "ring depth");
-  static_assert(NST == 2 || ((A3 ? TA::PER + TW::PER : (NST - 2) * D) + E < 64), "vmcnt range");
-  static_assert(!A3 || TW::FULLW * 64 == NTHR, "A3W2: every wave issues all its W DMA");
-  constexpr int LDS_ELEMS = A3 ? 3 * BM * KB + 2 * BNT * KB : NST * STG;
-  __shared__ __attribute__((aligned(16))) bf16_t lds[LDS_ELEMS];
+  static_assert(NST == 2 || NST == 3, "ring depth");
+  static_assert(NST == 2 || (NST - 2) * D + E < 64, "vmcnt range");
+  __shared__ __attribute__((aligned(16))) bf16_t lds[NST * STG];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave % WM, wn = wave / WM;  // this wave's 64 x 64 piece (tokens, columns)
   const int G = gridDim.x;
   const int L = xcd_remap(blockIdx.x, G);
   const int ntiles = a.tiles_m * a.tiles_n;
-  const int nk = a.K / KB;  // K % 64 == 0 (nt_shape_ok)
+  const int nk = a.K / BK;  // K % 64 == 0 (nt_shape_ok)
   const int mine = L < ntiles ? (ntiles - 1 - L) / G + 1 : 0;
   const int nsteps = mine * nk;
-  // NST = 2 walks tiles (tcur, then tnext): statically L, L + G, ..., or with the tile queue
-  // claims of this XCD's counter -- the same tiles xcd_remap gives the XCD (first tile x0 +
-  // local, then rounds of qx tiles G apart), in round order, so a row block of A still stays on
-  // one XCD's L2.  The next tile is claimed by thread 0 at a tile's first K step (after its
-  // barrier), published at the second (after that step's vmcnt(0)) through sq[ti & 1] and read
-  // after its barrier -- before the last step issues the next tile's first DMA (nk >= 2: the
-  // launch passes no queue for single-step tiles).
-  int* const tq = NST == 2 ? a.tq : nullptr;
-  const int xcd = blockIdx.x & 7;
-  const int qx = (G >> 3) + (xcd < (G & 7) ? 1 : 0);
-  const int x0 = L - (int)(blockIdx.x >> 3);
-  __shared__ int sq[2];
 
-  // K step kk of tile t: its A / W tiles -> LDS at dst
-  auto issue_a_t = [&](int t, int kk, bf16_t* dst) __attribute__((always_inline)) {
-    const int mt = t / a.tiles_n;
-    if (a.A2 == nullptr) TA::stage(a.A, mt * BM, a.M, a.K, kk * KB, dst, tid);
-    else if (kk * KB < a.K1) TA::stage(a.A, mt * BM, a.M, a.K1, kk * KB, dst, tid);  // K1 % 64 == 0
-    else TA::stage(a.A2, mt * BM, a.M, a.K - a.K1, kk * KB - a.K1, dst, tid);
-  };
-  auto issue_w_t = [&](int t, int kk, bf16_t* dst) __attribute__((always_inline)) {
-    const int mt = t / a.tiles_n, nt = t - mt * a.tiles_n;
-    if constexpr (WKN) TK::stage(a.W, nt * BNT, a.N, kk * KB, dst, tid);
-    else TW::stage(a.W, nt * BNT, a.N, a.K, kk * KB, dst, tid);
-  };
-  // K step s of this workgroup's static sequence
-  auto issue_a = [&](int s, bf16_t* dst) __attribute__((always_inline)) {
-    const int ti = s / nk;
-    issue_a_t(L + ti * G, s - ti * nk, dst);
-  };
-  auto issue_w = [&](int s, bf16_t* dst) __attribute__((always_inline)) {
-    const int ti = s / nk;
-    issue_w_t(L + ti * G, s - ti * nk, dst);
-  };
-  // K step kk of tile t -> ring stage `st` (NST = 2 / 3: A and W in one stage)
-  auto issue_tk = [&](int t, int kk, int st) __attribute__((always_inline)) {
+  // The next K step of this workgroup's sequence to stage (K step ik of tile it; the sequence
+  // is tile L, L + G, ..., nk steps each): its A and W tiles -> ring stage `st`.  Two counters
+  // rather than s / nk: no division by nk per staged step.
+  int ik = 0, it = L;
+  auto issue_next = [&](int st) __attribute__((always_inline)) {
+    const int mt = it / a.tiles_n, nt = it - mt * a.tiles_n;
     bf16_t* dst = lds + st * STG;
-    issue_a_t(t, kk, dst);
-    issue_w_t(t, kk, dst + BM * KB);
+    if (a.A2 == nullptr) TA::stage(a.A, mt * BM, a.M, a.K, ik * BK, dst, tid);
+    else if (ik * BK < a.K1) TA::stage(a.A, mt * BM, a.M, a.K1, ik * BK, dst, tid);  // K1 % 64 == 0
+    else TA::stage(a.A2, mt * BM, a.M, a.K - a.K1, ik * BK - a.K1, dst, tid);
+    if constexpr (WKN) TK::stage(a.W, nt * BNT, a.N, ik * BK, dst + BM * BK, tid);
+    else TW::stage(a.W, nt * BNT, a.N, a.K, ik * BK, dst + BM * BK, tid);
+    if (++ik == nk) {
+      ik = 0;
+      it += G;
+    }
   };
-  auto issue = [&](int s, int st) __attribute__((always_inline)) {
-    const int ti = s / nk;
-    issue_tk(L + ti * G, s - ti * nk, st);
-  };
-  bf16_t* const ldsW = lds + 3 * BM * KB;  // A3W2: the W stages after the three A stages
 
   f32x16 acc[NI][2];  // [column tile ni][token tile mi]: C^T, W rows on the accumulator rows
 #pragma unroll
@@ -231,26 +189,14 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{0};
 
-  if constexpr (A3) {
-    // A(0), W(0), A(1): step 0 waits for W(0) with A(1) in flight
-    if (nsteps > 0) {
-      issue_a(0, lds);
-      issue_w(0, ldsW);
-    }
-    if (nsteps > 1) issue_a(1, lds + BM * KB);
-  } else {
 #pragma unroll
-    for (int s = 0; s < NST - 1; ++s)
-      if (s < nsteps) issue(s, s);
-  }
+  for (int s = 0; s < NST - 1; ++s)
+    if (s < nsteps) issue_next(s);
   int kk = 0, ti = 0;  // K step within the tile, tile ordinal (within this workgroup)
-  int tcur = L, tnext = L + G;  // NST = 2: this tile, the next (tq: known from the tile's 2nd step)
-  int nn = 0;                   // thread 0 (tq): the claim in flight
   int cst = 0;         // LDS stage of step s
   int epi_age = 99;    // steps since the last epilogue (its stores follow that step's DMA issue)
-  bool a3_more_a = false;  // A3W2: this step also issued A(s + 2)
   bool epi_full = true;  // that epilogue issued all E stores of this wave (no ragged M / N edge)
-  for (int s = 0; NST == 2 ? tcur < ntiles : s < nsteps; ++s) {
+  for (int s = 0; s < nsteps; ++s) {
     // step s's DMA landed; younger DMAs (step s + 1) and epilogue stores issued after step s's
     // DMA may stay in flight (NST = 3, tiles of >= 3 K steps); else everything retires.
     // The counts must never exceed the ops really issued after step s's DMA: a wave whose last
@@ -258,22 +204,9 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
     // past N), so it does not count them -- counting them let that wave pass the barrier with
     // its share of step s's DMA still in flight, and the other waves read stale LDS (found as
     // run-to-run differences of the eager step with the side stream on, round 3)
-    if constexpr (A3) {
-      // W(s) landed (and A(s), issued a step earlier); A(s + 1), issued after W(s), and the
-      // stores of an epilogue that followed them may stay in flight
-      const bool younger = s + 1 < nsteps;
-      const bool stores = epi_age == 0 && epi_full;
-      if (younger && stores) wait_vmcnt<TA::PER + E>();
-      else if (younger) wait_vmcnt<TA::PER>();
-      else if (stores) wait_vmcnt<E>();
-      else wait_vmcnt<0>();
-    } else if constexpr (NST == 2) {
+    if constexpr (NST == 2) {
       wait_vmcnt<0>();
-      if (tq != nullptr && kk == 1 && tid == 0) {
-        sq[ti & 1] = nn;  // (nothing in flight here)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // landed before the raw barrier
-      }
-    } else if constexpr (NST == 3) {
+    } else {
       const bool younger = s + 1 < nsteps;
       const bool stores = epi_age <= 1 && nk >= 3 && epi_full;
       if (nk < 3) wait_vmcnt<0>();
@@ -286,16 +219,7 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
     asm volatile("" ::: "memory");  // done reading step s-1's stage (refilled below)
     ++epi_age;
     const bool last = kk + 1 == nk;
-    if (NST == 2 && tq != nullptr) {
-      if (kk == 0) {
-        if (tid == 0) nn = tq_claim(tq, xcd);
-      } else if (kk == 1) {
-        // read before this step's DMA issue: no LDS-DMA in flight
-        const int c = __builtin_amdgcn_readfirstlane(sq[ti & 1]);
-        tnext = x0 + G * (1 + c / qx) + c % qx;
-      }
-    }
-    const int t = NST == 2 ? tcur : L + ti * G;
+    const int t = L + ti * G;
     const int mt = t / a.tiles_n, nt = t - mt * a.tiles_n;
     const int m0 = mt * BM, n0 = nt * BNT;
     const int hh = lane >> 5;
@@ -322,33 +246,13 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
           }
         }
     }
-    const bf16_t* ta;
-    const bf16_t* tw;
-    bool more;  // DMA issued in this step (the epilogue's wait lets it stay in flight)
-    if constexpr (A3) {
-      // W(s + 1) into the W stage step s - 1 used, A(s + 2) into the A stage of step s - 1
-      const int wst = s & 1, ast = cst;  // cst: A stage of step s (s % 3)
-      const bool mw = s + 1 < nsteps, ma = s + 2 < nsteps;
-      if (mw) issue_w(s + 1, ldsW + (wst ^ 1) * BNT * KB);
-      if (ma) issue_a(s + 2, lds + (ast == 0 ? 2 : ast - 1) * BM * KB);
-      more = mw;
-      a3_more_a = ma;
-      ta = lds + ast * BM * KB;
-      tw = ldsW + wst * BNT * KB;
-      cst = cst + 1 == 3 ? 0 : cst + 1;
-    } else if constexpr (NST == 2) {
-      more = !last || tnext < ntiles;
-      if (more) issue_tk(last ? tnext : tcur, last ? 0 : kk + 1, cst ^ 1);
-      ta = lds + cst * STG;
-      tw = ta + BM * KB;
-      cst ^= 1;
-    } else {
-      more = s + NST - 1 < nsteps;
-      if (more) issue(s + NST - 1, cst == 0 ? NST - 1 : cst - 1);
-      ta = lds + cst * STG;
-      tw = ta + BM * KB;
-      cst = cst + 1 == NST ? 0 : cst + 1;
-    }
+    // step s + NST - 1 into the stage step s - 1 used; `more`: DMA issued in this step (the
+    // epilogue's wait lets it stay in flight)
+    const bool more = s + NST - 1 < nsteps;
+    if (more) issue_next(cst == 0 ? NST - 1 : cst - 1);
+    const bf16_t* ta = lds + cst * STG;
+    const bf16_t* tw = ta + BM * BK;
+    cst = cst + 1 == NST ? 0 : cst + 1;
     bf16x8 fw[2][NI], fx[2][2];
     auto rd = [&](int ks, int set) {
 #pragma unroll
@@ -381,20 +285,11 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
     }
     kk = 0;
     ++ti;
-    if constexpr (NST == 2) {
-      tcur = tnext;
-      tnext = tcur + G;  // (static; tq: replaced at the next tile's first step)
-    }
     epi_age = 0;
     epi_full = m0 + 64 * wm + 64 <= a.M && n0 + WNC * wn + WNC <= a.N;
     // the epilogue operands (and every older DMA) have landed; the DMA just issued may stay
     // in flight (NST = 3).  One wait, not one per exec-masked store branch.
-    if constexpr (A3) {
-      // the epilogue operands were loaded before this step's W(s + 1) / A(s + 2) DMAs
-      if (more && a3_more_a) wait_vmcnt<TW::PER + TA::PER>();
-      else if (more) wait_vmcnt<TW::PER>();
-      else wait_vmcnt<0>();
-    } else if (NST >= 3 && more) {
+    if (NST >= 3 && more) {
       if (wave < DW0) wait_vmcnt<D>();
       else wait_vmcnt<D - 1>();
     } else {
@@ -434,10 +329,8 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
             }
           }
           const u32x4 pk = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
-          // ablation 16: no output stores (results wrong; the never-true test keeps the MFMAs).
           // These 16-B stores cover 32 tokens x 32 B per instruction; an epilogue staged through
           // the consumed ring stage and stored as 192-B row pieces was neutral (r05z).
-          if constexpr ((MSU_EXP & 16) != 0) if (v[0] != 1.2345e-30f) continue;
           *reinterpret_cast<u32x4*>(a.Y + off) = pk;
           if constexpr (EPI == EPI_GELU_DUAL) {
             // GELU of the rounded pre-activation, as the unfused GELU kernel would see it
@@ -456,7 +349,6 @@ __global__ void __launch_bounds__(128 * WM) gemm_nt_kernel(NtArgs a) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{0};
   }
-  tq_finish(tq);
 }
 
 }  // namespace
@@ -469,14 +361,9 @@ namespace {
 // default): the persistent 2-barrier kernel everywhere.  A/B switch MSU_NT_PP, set by the Python
 // side at import: the ping-pong kernel measured 0.72-0.98x of the persistent one (r05g)
 int g_nt_pp = 0;
-// tile-form override for kernel-timing tools (msu_nt_gemm_mode bits 1-2): 0 = the cost model,
-// 1 = 128 x 192 (two workgroups per CU), 2 = 256 x 128 (three-stage ring), 3 = 128 x 128
+// tile-form override for tests and kernel-timing tools (msu_nt_gemm_mode bits 1-2): 0 = the cost
+// model, 1 = 128 x 192 (two workgroups per CU), 2 = 256 x 128 (three-stage ring), 3 = 128 x 128
 int g_nt_force = 0;
-// msu_nt_gemm_mode bit 3: the 256 x 192 tile on the A3W2 ring (gemm_nt_kernel NST = 4)
-int g_nt_a3 = 0;
-// msu_nt_gemm_mode bit 4: the two-stage kernel's tile queue (opt-in MSU_NT_DYN=1: the claim's
-// round trip costs 2-3 us on the short stage-2/3 launches and the step did not gain, r06q/r06r)
-int g_nt_dyn = 0;
 
 // BN of the ping-pong kernel for this shape, or 0 (gemm_nt_kernel takes it): exact tiling, and
 // rounds of tiles at least 3/4 full (the stage-3 shapes, 96-288 tiles of 256 rows on 256 CUs,
@@ -543,12 +430,11 @@ NtCfg nt_cfg(long M, int N, bool wkn) {
 }
 
 // What a launch of (M, N, K, epi, weight form) runs under the mode bits in force: tile rows (64 wm)
-// and columns, ring form (2, 3, or 4 = A3W2), ping-pong kernel or gemm_nt_kernel, tile counts, grid
-// and whether the two-stage kernel claims its tiles from the queue.  nt_launch launches exactly
-// this; msu_nt_gemm_plan2 reports it.
+// and columns, ring depth (2 or 3), ping-pong kernel or gemm_nt_kernel, tile counts and grid.
+// nt_launch launches exactly this; msu_nt_gemm_plan2 reports it.
 struct NtPlan {
   int wm, bn, nst;
-  bool pp, queue;
+  bool pp;
   int tiles_m, tiles_n;
   long tiles;
   unsigned grid;
@@ -559,7 +445,7 @@ NtPlan nt_plan(long M, int N, int K, int epi, bool wkn) {
   const long cus = msu_num_cus();
   const int pbn = pp_bn(M, N, K, epi, wkn);
   if (pbn) {
-    p.wm = pp::BM / 64; p.bn = pbn; p.nst = 2; p.pp = true; p.queue = false;
+    p.wm = pp::BM / 64; p.bn = pbn; p.nst = 2; p.pp = true;
     p.tiles_n = N / pbn;
     p.tiles_m = (int)(M / pp::BM);
     p.tiles = (long)p.tiles_m * p.tiles_n;
@@ -568,27 +454,23 @@ NtPlan nt_plan(long M, int N, int K, int epi, bool wkn) {
   }
   const NtCfg cfg = nt_cfg(M, N, wkn);
   p.wm = cfg.wm; p.bn = cfg.bn; p.pp = false;
-  p.nst = cfg.bn == 192 ? (cfg.wm == 4 && g_nt_a3 ? 4 : 2) : (cfg.wm == 4 ? 3 : 2);
+  p.nst = cfg.wm == 4 && cfg.bn == 128 ? 3 : 2;
   p.tiles_n = (N + cfg.bn - 1) / cfg.bn;
   p.tiles_m = (int)((M + 64 * cfg.wm - 1) / (64 * cfg.wm));
   p.tiles = (long)((M + 64 * cfg.wm - 1) / (64 * cfg.wm)) * p.tiles_n;
   const long cap = cus * (cfg.wm == 2 ? 2 : 1);
   p.grid = (unsigned)(p.tiles < cap ? p.tiles : cap);
-  p.queue = p.nst == 2 && g_nt_dyn && K >= 2 * BK;
   return p;
 }
 
-template <typename T, int WM, int NST, bool WKN, int BNT, int KB = 64>
+template <typename T, int WM, int NST, bool WKN, int BNT>
 void launch_nt(int epi, const NtPlan& p, const NtArgs& a, hipStream_t st) {
-  static_assert(KB == BK, "nt_plan's queue rule is in K steps of BK");
   const unsigned grid = p.grid;
   const dim3 blk(128 * WM);
-  NtArgs q = a;
-  q.tq = p.queue ? tile_queue(st) : nullptr;
   switch (epi) {
-    case EPI_PLAIN: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_PLAIN, WM, NST, WKN, BNT, KB>), dim3(grid), blk, 0, st, q); break;
-    case EPI_GELU_DUAL: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_GELU_DUAL, WM, NST, WKN, BNT, KB>), dim3(grid), blk, 0, st, q); break;
-    default: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_GELU_GRAD, WM, NST, WKN, BNT, KB>), dim3(grid), blk, 0, st, q); break;
+    case EPI_PLAIN: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_PLAIN, WM, NST, WKN, BNT>), dim3(grid), blk, 0, st, a); break;
+    case EPI_GELU_DUAL: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_GELU_DUAL, WM, NST, WKN, BNT>), dim3(grid), blk, 0, st, a); break;
+    default: hipLaunchKernelGGL((gemm_nt_kernel<T, EPI_GELU_GRAD, WM, NST, WKN, BNT>), dim3(grid), blk, 0, st, a); break;
   }
 }
 
@@ -600,7 +482,6 @@ int nt_launch(int dtype, const void* A, const void* W, const float* bias, void* 
   if (epi == EPI_GELU_GRAD && (H == nullptr || bias != nullptr)) return -3;
   if (epi < 0 || epi > 2) return -3;
   NtArgs a;
-  a.tq = nullptr;
   if (A2 != nullptr && (wkn || epi != EPI_PLAIN || K1 <= 0 || K1 >= K || K1 % 64)) return -3;
   a.A = (const bf16_t*)A;
   a.A2 = (const bf16_t*)A2;
@@ -626,8 +507,7 @@ int nt_launch(int dtype, const void* A, const void* W, const float* bias, void* 
   }
   MSU_DISPATCH16(dtype, T,
     if (p.bn == 192) {
-      if (p.nst == 4) launch_nt<T, 4, 4, false, 192>(epi, p, a, st);
-      else if (p.wm == 4) launch_nt<T, 4, 2, false, 192>(epi, p, a, st);
+      if (p.wm == 4) launch_nt<T, 4, 2, false, 192>(epi, p, a, st);
       else launch_nt<T, 2, 2, false, 192>(epi, p, a, st);
     } else if (p.wm == 4) {
       if (wkn) launch_nt<T, 4, 3, true, 128>(epi, p, a, st);
@@ -665,28 +545,26 @@ int msu_nt_gemm_plan(long M, int N) {
 }
 
 // Host only: what msu_nt_gemm (wkn = 0) / msu_nt_gemm_kn (wkn != 0) launch for this shape and
-// epilogue under the mode bits in force (nt_plan): out8 = {tile rows, tile columns, ring form (2:
-// two-stage, 3: three-stage, 4: A3W2), ping-pong kernel, tiles, grid, tile queue used, CU count}.
+// epilogue under the mode bits in force (nt_plan): out8 = {tile rows, tile columns, ring depth (2:
+// two-stage, 3: three-stage), ping-pong kernel, tiles, grid, 0 (once: tile queue used), CU count}.
 // -2 where the shape is not covered.
 int msu_nt_gemm_plan2(long M, int N, int K, int epi, int wkn, long* out8) {
   for (int i = 0; i < 8; ++i) out8[i] = 0;
   if (!nt_shape_ok(M, N, K) || epi < 0 || epi > 2) return -2;
   const NtPlan p = nt_plan(M, N, K, epi, wkn != 0);
   out8[0] = 64 * p.wm; out8[1] = p.bn; out8[2] = p.nst; out8[3] = p.pp; out8[4] = p.tiles; out8[5] = p.grid;
-  out8[6] = p.queue; out8[7] = msu_num_cus();
+  out8[7] = msu_num_cus();
   return 0;
 }
 
 // bit 0 -- 1: the ping-pong kernel where the shape tiles exactly, 0 (the default, MSU_NT_PP=0): the
-// persistent 2-barrier kernel everywhere; bits 1-2: a forced tile form for kernel-timing tools
-// (0: the cost model; 1: 128 x 192, 2: 256 x 128, 3: 128 x 128); bit 3: the 256 x 192 tile on the
-// A3W2 ring (A two K steps ahead).  Returns the previous mode.
+// persistent 2-barrier kernel everywhere; bits 1-2: a forced tile form for tests and kernel-timing
+// tools (0: the cost model; 1: 128 x 192, 2: 256 x 128, 3: 128 x 128).  Bits 3 and 4 once selected
+// the A3W2 ring and the tile queue: they are ignored and read back 0.  Returns the previous mode.
 int msu_nt_gemm_mode(int mode) {
-  const int prev = g_nt_pp | (g_nt_force << 1) | (g_nt_a3 << 3) | (g_nt_dyn << 4);
+  const int prev = g_nt_pp | (g_nt_force << 1);
   g_nt_pp = mode & 1;
   g_nt_force = (mode >> 1) & 3;
-  g_nt_a3 = (mode >> 3) & 1;
-  g_nt_dyn = (mode >> 4) & 1;
   return prev;
 }
 

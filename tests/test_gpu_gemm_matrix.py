@@ -27,9 +27,7 @@ through ``msu_tok_gemm_plan_epi`` / ``msu_nt_gemm_plan2``, the kernel form it is
                                workgroup walks ragged-N tiles only, three of them in a row
         128 x 192              (bits 1-2 = 1)       three epilogues; (1, 192), (100, 384), the large one
         256 x 192 two-stage    (cost model)         three epilogues; the large shape: N = 192 and
-        256 x 192 A3W2 ring    (the same, bit 3)    2 CUs + 3 tiles of 256 rows, the last ragged
-        tile queue             (bit 4) on every two-stage form at nk >= 2: bit-identical to the
-                               static schedule, also on a second stream
+                               2 CUs + 3 tiles of 256 rows, the last ragged
         ping-pong kernel       (bit 0) plain and GELU dual at nk in {3, 5}: exactly 3/4 of a round of
                                tiles (N = 192) and two rounds (N = 384)
       (the 192-wide forms need N % 192 == 0 and the cost model picks 256 x 192 only at large M,
@@ -74,8 +72,9 @@ Two kinds of case, both in every test:
 Sensitivity (references only, one per family): a reference with one 8-wide k chunk of W zeroed
 violates the Y bound on >= 50 % of the elements.
 
-Measured on an MI355X (profiles/r18a_gemm_matrix_ratios.txt, per family, form and dtype; the
-whole module: 183 tests in 6.4 s, the slowest 0.48 s -- the first launch of the process -- then
+Measured on an MI355X (profiles/r18a_gemm_matrix_ratios.txt, per family, form and dtype, taken
+when the NT kernel still had an A3W2 ring and a tile queue, both removed since; the whole
+module: 183 tests in 6.4 s, the slowest 0.48 s -- the first launch of the process -- then
 0.20 s for the predicate sweep's 3344 launches and 0.07 s for a large NT case).
 
 kappa: the reference's f32 matmul reaches 7.61 x 2^-24 A at tok/plain-kc96-nc64-nst2-nw8, f16,
@@ -106,8 +105,8 @@ Two scratch builds (not kept):
     all 604 of test_gpu_nt_gemm.py passed.  It is a race: the over-counted wait lets a ragged wave
     pass the barrier with its share of a K step's DMA in flight, and that DMA was issued a whole
     step earlier; on an otherwise idle device it has landed by then.  The cases that would show it
-    (256 x 128 three-stage and A3W2 at nk = 3, 5 on the large shapes: odd workgroups walk three
-    ragged-N tiles in a row, every launch repeated and compared bit for bit) are in place.
+    (256 x 128 three-stage at nk = 3, 5 on the large shapes: odd workgroups walk three ragged-N
+    tiles in a row, every launch repeated and compared bit for bit) are in place.
 
 Found by this module: nothing in the kernels; every form of the matrix meets the rule above.  From
 the source (and fixed with this module): ``tok_plan`` planned the GELU epilogues and split A at the
@@ -481,10 +480,10 @@ def test_tok_predicate_agrees_with_launch():
 NKS = (1, 2, 3, 5)
 # form -> (mode bits, rows, columns, ring, KN and split-A variants)
 NT_FORMS = {"128x128": (6, 128, 128, 2, True), "256x128": (4, 256, 128, 3, True), "128x192": (2, 128, 192, 2, False),
-            "256x192": (0, 256, 192, 2, False), "256x192a3": (8, 256, 192, 4, False)}
+            "256x192": (0, 256, 192, 2, False)}
 # shape group -> [(shape name, forms run on it)]
 NT_SHAPES = {"n128": [("one", ("128x128", "256x128")), ("ragged", ("128x128", "256x128")), ("large", ("128x128", "256x128"))],
-             "n192": [("one", ("128x192",)), ("ragged", ("128x192",)), ("large", ("128x192", "256x192", "256x192a3"))]}
+             "n192": [("one", ("128x192",)), ("ragged", ("128x192",)), ("large", ("128x192", "256x192"))]}
 NT_CASES = [(grp, sh, dt, nk) for grp in NT_SHAPES for sh, _ in NT_SHAPES[grp] for dt in DTYPES for nk in NKS]
 PP_CASES = [(sh, dt, nk) for sh in ("three_quarters", "two_rounds") for dt in DTYPES for nk in (3, 5)]
 
@@ -520,10 +519,10 @@ def _nt_shape(lib, grp, sh, K):
     return M, 192
 
 
-def _nt_call(o, layout, epi, bias, K1, y, y2, wk, stream=None):
+def _nt_call(o, layout, epi, bias, K1, y, y2, wk):
     ops = _ops()
     lib = _L().lib()
-    st = ops._s(o.a) if stream is None else stream
+    st = ops._s(o.a)
     dtc, b, h = ops._dt(o.a), ops._p(o.b if bias else None), ops._p(o.h if epi == GRAD else None)
     if K1:
         return lib.msu_nt_gemm_cat(dtc, ops._p(o.a1[K1]), ops._p(o.a2[K1]), K1, ops._p(o.w), b, ops._p(y), o.M, o.N, o.K, st)
@@ -531,10 +530,10 @@ def _nt_call(o, layout, epi, bias, K1, y, y2, wk, stream=None):
     return fn(dtc, ops._p(o.a), ops._p(w), b, ops._p(y), ops._p(y2), h, o.M, o.N, o.K, epi, st)
 
 
-def _nt_launch(o, tag, layout, epi, bias, K1, wk, stream=None):
+def _nt_launch(o, tag, layout, epi, bias, K1, wk):
     y = Band(o.M * o.N, o.dtype)
     y2 = Band(o.M * o.N, o.dtype) if epi == DUAL else None
-    rc = _nt_call(o, layout, epi, bias, K1, y.t, y2.t if y2 else None, wk, stream)
+    rc = _nt_call(o, layout, epi, bias, K1, y.t, y2.t if y2 else None, wk)
     assert rc == 0, f"{tag}: returned {rc}"
     torch.cuda.synchronize()
     return y.check(tag + " Y"), (y2.check(tag + " Y2") if y2 else None)
@@ -565,7 +564,6 @@ def test_nt_gemm_matrix(case):
     prev = lib.msu_nt_gemm_mode(0)
     try:
         M, N = _nt_shape(lib, grp, sh, K)
-        side = torch.cuda.Stream()
         for exact in (True, False):
             o, wk = _nt_operands(dt, M, N, K, exact, sorted({64, K - 64}) if nk >= 2 and grp == "n128" else ())
             o.tag = tag0 = f"nt/{grp}-{sh}/{M}x{N}x{K}/{DTNAME[dt]}/{'exact' if exact else 'round'}"
@@ -586,16 +584,6 @@ def test_nt_gemm_matrix(case):
                     if epi == DUAL:
                         _same(tag + " Y2", y2, y2b)
                     _nt_judge(o, tag, epi, bias, y, y2)
-                    if ring == 2 and nk >= 2:  # the tile queue: the static schedule's bits, on two streams
-                        _set_mode(lib, mode | 16)
-                        assert nt_plan(M, N, K, epi, layout == "kn")["queue"] == 1, tag
-                        yq, y2q = _nt_launch(o, tag + "/queue", layout, epi, bias, K1, wk)
-                        side.wait_stream(torch.cuda.current_stream())
-                        ys, y2s = _nt_launch(o, tag + "/queue-side", layout, epi, bias, K1, wk, side.cuda_stream)
-                        for u, r in ((yq, y), (ys, y), (y2q, y2), (y2s, y2)):
-                            if r is not None:
-                                _same(tag + " queue vs static", u, r)
-                        _note("nt_queue", dt, 0.0, tag)
     finally:
         lib.msu_nt_gemm_mode(prev)
 
@@ -822,8 +810,6 @@ def _assert_coverage():
         for form in dict(NT_SHAPES[grp])[sh]:
             for layout, epi, bias, K1 in _nt_variants(form, nk):
                 got.add((form, layout, epi, bool(K1), sh, nk, dt))
-                if NT_FORMS[form][3] == 2 and nk >= 2:
-                    got.add((form + "+queue", layout, epi, bool(K1), sh, nk, dt))
     want = set()
     for dt in DTYPES:
         for nk in NKS:
@@ -834,11 +820,7 @@ def _assert_coverage():
                         want.add((form, "nk", PLAIN, True, sh, nk, dt))
             for sh in ("one", "ragged", "large"):
                 want |= {("128x192", "nk", epi, False, sh, nk, dt) for epi in (PLAIN, DUAL, GRAD)}
-            for form in ("256x192", "256x192a3"):
-                want |= {(form, "nk", epi, False, "large", nk, dt) for epi in (PLAIN, DUAL, GRAD)}
-            if nk >= 2:
-                for form in ("128x128", "128x192", "256x192"):
-                    want |= {(form + "+queue", "nk", epi, False, "large", nk, dt) for epi in (PLAIN, DUAL, GRAD)}
+            want |= {("256x192", "nk", epi, False, "large", nk, dt) for epi in (PLAIN, DUAL, GRAD)}
     assert want <= got, sorted(map(str, want - got))
     assert {(sh, dt, nk) for sh, dt, nk in PP_CASES} == {(sh, dt, nk) for sh in ("three_quarters", "two_rounds")
                                                           for dt in DTYPES for nk in (3, 5)}

@@ -8,9 +8,11 @@ the persistent tiled NT GEMM (csrc/gemm_nt.hip), never to the library GEMM, unle
 MSU_GEMM_ROUTE=lib A/B switch asks for it.  The routing queries are host functions of the C-ABI
 library (no GPU needed).
 """
+import ctypes
+
 import pytest
 
-from semantic_segmentation_of_stylegan2_artifacts_amd import ops
+from semantic_segmentation_of_stylegan2_artifacts_amd import _lib, ops
 
 
 def _shapes(C, B, img):
@@ -62,3 +64,96 @@ def test_the_48_deep_token_stage_takes_the_plain_epilogue_only(monkeypatch):
         assert ops.gemm_route(M, 96, K, ops.TOK_GELU_DUAL) != "tok"
         assert ops._cat_route(M, 96, K, K // 2) != "tok"
     assert ops.tok_supported_cat(M, 96, 192) and ops._cat_route(M, 96, 192, 96) == "tok"
+
+
+# (M, N, wkn) -> (tile rows, tile columns, ring depth, tiles, grid) of the NT GEMM on 256 CUs (the
+# MI355X's count, and the library's fallback where no device answers): what the cost model and the
+# grid sizing of csrc/gemm_nt.hip gave at 5a430d0, before the kernel's A3W2 ring and tile queue
+# were removed, at mode 0.  The 18 production shapes of tools/nt_shapes.py, SHAPES + BIG (both weight
+# layouts) and WIDE of tests/test_gpu_nt_gemm.py, and its three underfilled shapes.
+NT_PLANS = [
+    ((131072, 576, 0), (256, 192, 2, 1536, 256)),
+    ((131072, 192, 0), (256, 192, 2, 512, 256)),
+    ((131072, 768, 0), (256, 192, 2, 2048, 256)),
+    ((32768, 1152, 0), (256, 192, 2, 768, 256)),
+    ((32768, 384, 0), (256, 192, 2, 256, 256)),
+    ((32768, 1536, 0), (256, 192, 2, 1024, 256)),
+    ((32768, 768, 0), (256, 192, 2, 512, 256)),
+    ((8192, 2304, 0), (256, 192, 2, 384, 256)),
+    ((8192, 768, 0), (128, 192, 2, 256, 256)),
+    ((8192, 3072, 0), (256, 192, 2, 512, 256)),
+    ((32768, 384, 1), (256, 128, 3, 384, 256)),
+    ((131072, 192, 1), (256, 128, 3, 1024, 256)),
+    ((4096, 1152, 0), (128, 192, 2, 192, 192)),
+    ((4096, 1152, 1), (256, 128, 3, 144, 144)),
+    ((4096, 384, 0), (128, 128, 2, 96, 96)),
+    ((4096, 384, 1), (128, 128, 2, 96, 96)),
+    ((1000, 384, 0), (128, 128, 2, 24, 24)),
+    ((1000, 384, 1), (128, 128, 2, 24, 24)),
+    ((2048, 768, 0), (128, 128, 2, 96, 96)),
+    ((2048, 768, 1), (128, 128, 2, 96, 96)),
+    ((777, 192, 0), (128, 128, 2, 14, 14)),
+    ((777, 192, 1), (128, 128, 2, 14, 14)),
+    ((300, 2304, 0), (128, 128, 2, 54, 54)),
+    ((300, 2304, 1), (128, 128, 2, 54, 54)),
+    ((128, 768, 0), (128, 128, 2, 6, 6)),
+    ((128, 768, 1), (128, 128, 2, 6, 6)),
+    ((513, 96, 0), (128, 128, 2, 5, 5)),
+    ((513, 96, 1), (128, 128, 2, 5, 5)),
+    ((64, 160, 0), (128, 128, 2, 2, 2)),
+    ((64, 160, 1), (128, 128, 2, 2, 2)),
+    ((1, 32, 0), (128, 128, 2, 1, 1)),
+    ((1, 32, 1), (128, 128, 2, 1, 1)),
+    ((32768, 1152, 1), (256, 128, 3, 1152, 256)),
+    ((32077, 416, 0), (256, 128, 3, 504, 256)),
+    ((32077, 416, 1), (256, 128, 3, 504, 256)),
+    ((65536, 640, 0), (256, 128, 3, 1280, 256)),
+    ((65536, 640, 1), (256, 128, 3, 1280, 256)),
+    ((32077, 384, 0), (256, 192, 2, 252, 252)),
+    ((32077, 384, 1), (256, 128, 3, 378, 256)),
+    ((8187, 576, 0), (128, 192, 2, 192, 192)),
+]
+
+
+def _nt_plan(M, N, K, wkn, epi=0):
+    """(rc, (rows, columns, ring, tiles, grid), ping-pong kernel, tile-queue field, CU count) of msu_nt_gemm_plan2."""
+    out = (ctypes.c_long * 8)()
+    rc = _lib.lib().msu_nt_gemm_plan2(M, N, K, epi, wkn, out)
+    return rc, (out[0], out[1], out[2], out[4], out[5]), out[3], out[6], out[7]
+
+
+def test_nt_plan_table_is_unchanged():
+    """nt_cfg's cost model and the grid sizing, pinned shape by shape; at mode 0 neither K nor the
+    epilogue enters, and the field that reported the tile queue is 0."""
+    lib = _lib.lib()
+    prev = lib.msu_nt_gemm_mode(0)
+    try:
+        for (M, N, wkn), want in NT_PLANS:
+            for K, epi in ((64, 0), (384, 1), (3072, 2)):
+                got = _nt_plan(M, N, K, wkn, epi)
+                assert got == (0, want, 0, 0, 256), ((M, N, K, wkn, epi), got, want)
+    finally:
+        lib.msu_nt_gemm_mode(prev)
+    assert _nt_plan(4096, 100, 384, 0)[0] == -2  # N % 32
+    assert _nt_plan(4096, 384, 96, 1)[0] == -2   # K % 64
+    assert _lib.plan_nt(8192, 768) == (128, 192, False) and _lib.plan_nt(32768, 1152) == (256, 192, False)
+
+
+def test_nt_mode_ignores_the_removed_bits():
+    """msu_nt_gemm_mode: bit 0 (the ping-pong kernel) and bits 1-2 (the forced tile form) are kept;
+    bits 3 and 4 (once the A3W2 ring and the tile queue) are ignored and read back 0."""
+    lib = _lib.lib()
+    prev = lib.msu_nt_gemm_mode(0x18)
+    try:
+        assert lib.msu_nt_gemm_mode(6) == 0
+        assert lib.msu_nt_gemm_mode(0x1f) == 6
+        assert lib.msu_nt_gemm_mode(0x18) == 7
+        # with the stale bits set a launch is planned as at mode 0
+        assert _nt_plan(32768, 384, 384, 0) == (0, (256, 192, 2, 256, 256), 0, 0, 256)
+        # forced forms, as the tests and tools reach them: 1 -> 128 x 192, 2 -> 256 x 128, 3 -> 128 x 128
+        for mode, want in ((2, (128, 192, 2)), (4, (256, 128, 3)), (6, (128, 128, 2)), (0, (256, 192, 2))):
+            lib.msu_nt_gemm_mode(mode)
+            assert _nt_plan(32768, 384, 384, 0)[1][:3] == want, mode
+    finally:
+        lib.msu_nt_gemm_mode(prev)
+    assert lib.msu_nt_gemm_mode(prev) == prev

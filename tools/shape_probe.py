@@ -38,7 +38,7 @@ def timed(fn):
 
 arms = [(f"nt F{f}", f) for f in (0, 1, 2, 3)]
 for name, f in arms:
-    L.msu_nt_gemm_mode((prev & 17) | (f << 1))
+    L.msu_nt_gemm_mode((prev & 1) | (f << 1))
     us, err = timed(lambda: ops.nt_gemm(a, w, None))
     print(f"{name:8s} M={M} N={N} K={K}: {us:8.1f} us {2.0 * M * N * K / us / 1e6:7.1f} TF/s "
           f"{(M * K + N * K + M * N) * 2 / us / 1e3:7.1f} GB/s  rel err {err:.1e}", flush=True)
