@@ -406,6 +406,25 @@ int msu_adamw_dev(float* p, const float* g, float* m, float* v, long n, const do
 int msu_adamw_dev2(float* p, float* g, float* m, float* v, long n, const double* hyper, double beta1, double beta2,
                    double eps, double weight_decay, const float* inv_scale, const float* found_inf, void* shadow,
                    int shadow_dtype, int zero_grad, void* stream);
+/* msu_adamw_dev2 that also keeps an exponential moving average of the parameters, in the same pass:
+ * after the new value pn went to p (and the shadow), with w = (float)(1.0 - ema_decay) and e = ema[i],
+ *   ema[i] = w < 0.5f ? e + w * (pn - e) : pn - (pn - e) * (1.f - w)       (f32, unfused)
+ * i.e. ATen's ema.lerp_(p, 1 - ema_decay) (timm ModelEmaV2, swa_utils.get_ema_multi_avg_fn); decay 0
+ * leaves ema bitwise p.  p, g, m, v and the shadow come out bitwise as from msu_adamw_dev2.  A skipped
+ * step (found_inf[0] != 0) does not touch ema: the average advances with the applied steps only.
+ * ema f32 [n], no alias of the other buffers.  -2, nothing launched: hyper or ema null, ema_decay
+ * outside [0, 1) or NaN, shadow non-null with a dtype that is not 16-bit.  n == 0: 0. */
+int msu_adamw_dev3(float* p, float* g, float* m, float* v, float* ema, long n, const double* hyper,
+                   double beta1, double beta2, double eps, double weight_decay, double ema_decay,
+                   const float* inv_scale, const float* found_inf, void* shadow, int shadow_dtype,
+                   int zero_grad, void* stream);
+/* In-place exchange of two flat f32 buffers, (a[i], b[i]) = (b[i], a[i]) for i < n as bit patterns,
+ * and, shadow non-null, shadow[i] = the new a[i] rounded to shadow_dtype (1 bf16 / 2 f16, the cast of
+ * msu_adamw_dev2): the trainer swaps its weights with their moving average for an evaluation and
+ * back, every pointer a captured step holds stays valid.  One pass, 16-B loads and stores, any
+ * n >= 0.  -2, nothing launched: a or b null, n < 0, a / b / shadow not 16-byte aligned, [a, a + n)
+ * and [b, b + n) overlapping, shadow non-null with a dtype that is not 16-bit. */
+int msu_swap_cast(float* a, float* b, void* shadow, int shadow_dtype, long n, void* stream);
 /* hyper[1] += 1 unless found_inf[0] != 0 (the skipped step does not count, as torch's AdamW
  * `step` state is not advanced when GradScaler skips optimizer.step). */
 int msu_step_advance(double* hyper, const float* found_inf, void* stream);

@@ -65,6 +65,8 @@ SIGNATURES = {
     "msu_grad_clip_scale": (I, [P, I, P, D, P, P, P]),
     "msu_adamw_dev": (I, [P, P, P, P, L, P, D, D, D, D, P, P, P]),
     "msu_adamw_dev2": (I, [P, P, P, P, L, P, D, D, D, D, P, P, P, I, I, P]),
+    "msu_adamw_dev3": (I, [P, P, P, P, P, L, P, D, D, D, D, D, P, P, P, I, I, P]),
+    "msu_swap_cast": (I, [P, P, P, I, L, P]),
     "msu_step_advance": (I, [P, P, P]),
     "msu_loss_scale_step": (I, [P, P, P, P, P, P, D, D, I, P]),
     "msu_cast": (I, [I, P, P, L, P]),

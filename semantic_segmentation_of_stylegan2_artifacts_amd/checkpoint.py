@@ -6,7 +6,8 @@
 * ``save_last`` -- the last-epoch payload ``{"epoch", "model", "optimizer", "iter_num",
   "dice"}`` (trainer.py:403-409) with the optimizer state in ``torch.optim.AdamW`` format;
 * ``load_checkpoint`` -- test.py:96-110: ``{"model": sd}``, ``{"state_dict": sd}`` or a bare
-  state dict, loaded with ``strict=True``;
+  state dict, loaded with ``strict=True`` (``use_ema``: the ``"model_ema"`` weights that
+  ``save_best`` / ``save_last`` add when given ``Trainer.ema_state_dict()``);
 * ``remap_segface`` / ``remap_imagenet1k`` -- the key maps of ``MSUNet.load_segface_weight``
   and ``MSUNet.load_IMAGENET1K_weight`` (network/MSUNet.py:61-229): SegFace
   ``state_dict_backbone`` ``backbone.0.*`` and torchvision swin_b ``features.*`` keys onto the
@@ -32,9 +33,17 @@ def core(model):
     return model.module if isinstance(model, torch.nn.DataParallel) else model
 
 
-def save_best(model, epoch, best_score, log_save_path, name="best_model.pth"):
-    """trainer.py:365-379: tmp file + os.replace, legacy serialization."""
+def _cpu_copy(state):
+    return {k: v.detach().to("cpu", copy=True) for k, v in state.items()}
+
+
+def save_best(model, epoch, best_score, log_save_path, name="best_model.pth", ema_state=None):
+    """trainer.py:365-379: tmp file + os.replace, legacy serialization.  ema_state
+    (``Trainer.ema_state_dict()``) adds a ``"model_ema"`` key; without one the payload is the
+    reference's, key for key (its loaders ignore keys they do not know)."""
     payload = {"model": _cpu_state(core(model)), "epoch": epoch, "best_score": best_score}
+    if ema_state is not None:
+        payload["model_ema"] = _cpu_copy(ema_state)
     best_path = os.path.join(log_save_path, name)
     tmp = best_path + ".tmp"
     torch.save(payload, tmp, _use_new_zipfile_serialization=False)
@@ -42,25 +51,33 @@ def save_best(model, epoch, best_score, log_save_path, name="best_model.pth"):
     return best_path
 
 
-def save_last(model, optimizer_state, epoch, iter_num, dice, log_save_path, scaler_state=None):
+def save_last(model, optimizer_state, epoch, iter_num, dice, log_save_path, scaler_state=None, ema_state=None):
     """trainer.py:403-409 (``epoch_<n>.pth``).  scaler_state (``Trainer.scaler_state_dict()``, the
-    f16 loss scale in ``GradScaler.state_dict()`` format) adds a ``"scaler"`` key; without one the
-    payload is the reference's, key for key."""
+    f16 loss scale in ``GradScaler.state_dict()`` format) adds a ``"scaler"`` key and ema_state
+    (``Trainer.ema_state_dict()``, the averaged weights in the model's layout) a ``"model_ema"``
+    key; without them the payload is the reference's, key for key."""
     path = os.path.join(log_save_path, "epoch_" + str(epoch) + ".pth")
     payload = {"epoch": epoch, "model": _cpu_state(core(model)), "optimizer": optimizer_state,
                "iter_num": iter_num, "dice": dice}
     if scaler_state:
         payload["scaler"] = dict(scaler_state)
+    if ema_state is not None:
+        payload["model_ema"] = _cpu_copy(ema_state)
     torch.save(payload, path)
     return path
 
 
-def load_checkpoint(model, path, map_location="cpu", strict=True):
-    """test.py:96-110: the state dict under 'model' / 'state_dict' or the bare dict; strict."""
+def load_checkpoint(model, path, map_location="cpu", strict=True, use_ema=False):
+    """test.py:96-110: the state dict under 'model' / 'state_dict' or the bare dict; strict.
+    use_ema: the averaged weights under 'model_ema' instead (KeyError when the file has none)."""
     if not os.path.exists(path):
         raise FileNotFoundError(f"Checkpoint not found: {path}")
     ckpt = torch.load(path, map_location=map_location, weights_only=True)
-    if isinstance(ckpt, dict) and "model" in ckpt:
+    if use_ema:
+        if not (isinstance(ckpt, dict) and "model_ema" in ckpt):
+            raise KeyError(f"'model_ema' not found in checkpoint {path} (saved without ema_state)")
+        state = ckpt["model_ema"]
+    elif isinstance(ckpt, dict) and "model" in ckpt:
         state = ckpt["model"]
     elif isinstance(ckpt, dict) and "state_dict" in ckpt:
         state = ckpt["state_dict"]

@@ -241,13 +241,17 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
 // 1 - b2); param.addcdiv_(exp_avg, sqrt(exp_avg_sq) / sqrt(bc2) + eps, -lr / bc1)).
 // S: the 16-bit shadow written with the updated parameter (void: none); ZERO: the gradient is
 // zeroed after it was read (also on a skipped step) -- the step's gradient reset and bf16 shadow
-// refresh in the same pass instead of a fill and a re-read of the parameters
-template <typename S, bool ZERO>
+// refresh in the same pass instead of a fill and a re-read of the parameters.
+// EMA: an exponential moving average of the parameters rides in the same pass, ema.lerp_(p, 1 -
+// ema_decay) on the value just written to p (timm ModelEmaV2, swa_utils.get_ema_multi_avg_fn;
+// decay 0: bitwise p); a skipped step leaves it alone, as it leaves p and the step count
+template <typename S, bool ZERO, bool EMA>
 __global__ void __launch_bounds__(256) adamw_dev_kernel(float* __restrict__ p, float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long n,
                                                         const double* hyper, double b1, double b2, float eps,
                                                         double wd, const float* inv_scale,
-                                                        const float* found_inf, S* __restrict__ shadow) {
+                                                        const float* found_inf, S* __restrict__ shadow,
+                                                        float* __restrict__ ema, double ema_decay) {
 #pragma clang fp contract(off)
   if (found_inf && found_inf[0] != 0.f) {
     if constexpr (ZERO)
@@ -262,6 +266,7 @@ __global__ void __launch_bounds__(256) adamw_dev_kernel(float* __restrict__ p, f
   const float neg_step_size = (float)(-(lr / (1.0 - pow(b1, step))));
   const float bc2_sqrt = (float)sqrt(1.0 - pow(b2, step));
   const float is = inv_scale ? inv_scale[0] : 1.f;
+  const float we = (float)(1.0 - ema_decay);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float gi = inv_scale ? g[i] * is : g[i];
     const float pi = p[i] * decay;
@@ -275,6 +280,10 @@ __global__ void __launch_bounds__(256) adamw_dev_kernel(float* __restrict__ p, f
     p[i] = pn;
     if constexpr (!std::is_void_v<S>) shadow[i] = from_f32<S>(pn);  // the cast copy_shadow made
     if constexpr (ZERO) g[i] = 0.f;
+    if constexpr (EMA) {
+      const float e = ema[i];
+      ema[i] = we < 0.5f ? e + we * (pn - e) : pn - (pn - e) * (1.f - we);  // ATen lerp(e, pn, we)
+    }
   }
 }
 
@@ -324,6 +333,31 @@ __global__ void __launch_bounds__(256) nonfinite_kernel(const float* x, long n, 
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
     bad |= !isfinite(x[i]);
   if (__any(bad) && (threadIdx.x & 63) == 0) flag[0] = 1.f;
+}
+
+// (a, b) = (b, a) in place, and the 16-bit shadow of the new a (the AdamW pass's cast) in the same
+// pass: 16-B loads and stores over n4 = n / 4 quads (8-B shadow stores), block 0 moves the
+// n % 4 tail.  S void: no shadow.
+template <typename S>
+__global__ void __launch_bounds__(256) swap_cast_kernel(float* __restrict__ a, float* __restrict__ b,
+                                                        S* __restrict__ shadow, long n4, int tail) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 va = *reinterpret_cast<const float4*>(a + 4 * i);
+    const float4 vb = *reinterpret_cast<const float4*>(b + 4 * i);
+    *reinterpret_cast<float4*>(a + 4 * i) = vb;
+    *reinterpret_cast<float4*>(b + 4 * i) = va;
+    if constexpr (!std::is_void_v<S>) {
+      const float w[4] = {vb.x, vb.y, vb.z, vb.w};
+      Vec4<S>::store(shadow + 4 * i, w);
+    }
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
+    const long i = 4 * n4 + threadIdx.x;
+    const float va = a[i], vb = b[i];
+    a[i] = vb;
+    b[i] = va;
+    if constexpr (!std::is_void_v<S>) shadow[i] = from_f32<S>(vb);
+  }
 }
 
 template <typename T>
@@ -506,9 +540,37 @@ int msu_adamw_dev(float* p, const float* g, float* m, float* v, long n, const do
                   void* stream) {
   if (n == 0) return 0;
   if (hyper == nullptr) return -2;
-  hipLaunchKernelGGL((adamw_dev_kernel<void, false>), dim3(grid_for(n, 256, 16384)), dim3(256), 0,
+  hipLaunchKernelGGL((adamw_dev_kernel<void, false, false>), dim3(grid_for(n, 256, 16384)), dim3(256), 0,
                      (hipStream_t)stream, p, const_cast<float*>(g), m, v, n, hyper, beta1, beta2, (float)eps,
-                     weight_decay, inv_scale, found_inf, (void*)nullptr);
+                     weight_decay, inv_scale, found_inf, (void*)nullptr, (float*)nullptr, 0.0);
+  return MSU_CHECK_LAUNCH();
+}
+
+// the trainer's optimizer pass, with (ema non-null) or without the parameters' moving average
+static int adamw_dev_launch(float* p, float* g, float* m, float* v, float* ema, long n, const double* hyper,
+                            double beta1, double beta2, double eps, double weight_decay, double ema_decay,
+                            const float* inv_scale, const float* found_inf, void* shadow, int shadow_dtype,
+                            int zero_grad, void* stream) {
+  const dim3 grid(grid_for(n, 256, 16384));
+  hipStream_t st = (hipStream_t)stream;
+#define MSU_ADAMW(S, Z, E)                                                                                      \
+  hipLaunchKernelGGL((adamw_dev_kernel<S, Z, E>), grid, dim3(256), 0, st, p, g, m, v, n, hyper, beta1, beta2,   \
+                     (float)eps, weight_decay, inv_scale, found_inf, (S*)shadow, ema, ema_decay)
+#define MSU_ADAMW_ZE(S)                                   \
+  if (ema != nullptr) {                                   \
+    if (zero_grad) MSU_ADAMW(S, true, true);              \
+    else MSU_ADAMW(S, false, true);                       \
+  } else {                                                \
+    if (zero_grad) MSU_ADAMW(S, true, false);             \
+    else MSU_ADAMW(S, false, false);                      \
+  }
+  if (shadow == nullptr) {
+    MSU_ADAMW_ZE(void)
+  } else {
+    MSU_DISPATCH16(shadow_dtype, T, MSU_ADAMW_ZE(T));
+  }
+#undef MSU_ADAMW_ZE
+#undef MSU_ADAMW
   return MSU_CHECK_LAUNCH();
 }
 
@@ -517,18 +579,39 @@ int msu_adamw_dev2(float* p, float* g, float* m, float* v, long n, const double*
                    int shadow_dtype, int zero_grad, void* stream) {
   if (n == 0) return 0;
   if (hyper == nullptr || (shadow != nullptr && !msu_is16(shadow_dtype))) return -2;
-  const dim3 grid(grid_for(n, 256, 16384));
+  return adamw_dev_launch(p, g, m, v, nullptr, n, hyper, beta1, beta2, eps, weight_decay, 0.0, inv_scale,
+                          found_inf, shadow, shadow_dtype, zero_grad, stream);
+}
+
+int msu_adamw_dev3(float* p, float* g, float* m, float* v, float* ema, long n, const double* hyper,
+                   double beta1, double beta2, double eps, double weight_decay, double ema_decay,
+                   const float* inv_scale, const float* found_inf, void* shadow, int shadow_dtype,
+                   int zero_grad, void* stream) {
+  if (hyper == nullptr || ema == nullptr || !(ema_decay >= 0.0 && ema_decay < 1.0) ||
+      (shadow != nullptr && !msu_is16(shadow_dtype)))
+    return -2;
+  if (n == 0) return 0;
+  return adamw_dev_launch(p, g, m, v, ema, n, hyper, beta1, beta2, eps, weight_decay, ema_decay, inv_scale,
+                          found_inf, shadow, shadow_dtype, zero_grad, stream);
+}
+
+int msu_swap_cast(float* a, float* b, void* shadow, int shadow_dtype, long n, void* stream) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  if (a == nullptr || b == nullptr || n < 0 || ((pa | pb | (uintptr_t)shadow) & 15) != 0 ||
+      (shadow != nullptr && !msu_is16(shadow_dtype)))
+    return -2;
+  if (pa < pb + 4 * (uintptr_t)n && pb < pa + 4 * (uintptr_t)n) return -2;  // overlapping ranges
+  if (n == 0) return 0;
+  const long n4 = n / 4;
+  const int tail = (int)(n % 4);
+  const dim3 grid(grid_for(n4));
   hipStream_t st = (hipStream_t)stream;
-#define MSU_ADAMW(S, Z)                                                                                         \
-  hipLaunchKernelGGL((adamw_dev_kernel<S, Z>), grid, dim3(256), 0, st, p, g, m, v, n, hyper, beta1, beta2,      \
-                     (float)eps, weight_decay, inv_scale, found_inf, (S*)shadow)
   if (shadow == nullptr) {
-    if (zero_grad) MSU_ADAMW(void, true);
-    else MSU_ADAMW(void, false);
+    hipLaunchKernelGGL(swap_cast_kernel<void>, grid, dim3(256), 0, st, a, b, (void*)nullptr, n4, tail);
   } else {
-    MSU_DISPATCH16(shadow_dtype, T, if (zero_grad) MSU_ADAMW(T, true); else MSU_ADAMW(T, false));
+    MSU_DISPATCH16(shadow_dtype, T,
+                   hipLaunchKernelGGL(swap_cast_kernel<T>, grid, dim3(256), 0, st, a, b, (T*)shadow, n4, tail));
   }
-#undef MSU_ADAMW
   return MSU_CHECK_LAUNCH();
 }
 

@@ -2161,11 +2161,27 @@ def grad_clip_scale_(part, inv_in, max_norm, norm_out, inv_out):
 
 
 def adamw_dev_(param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2, eps, weight_decay, inv_scale=None,
-               found_inf=None, shadow=None, zero_grad=False):
+               found_inf=None, shadow=None, zero_grad=False, ema=None, ema_decay=None):
     """AdamW over flat f32 buffers with lr and step read from the device tensor
     ``hyper = [lr, step]`` (f64); no update at all when found_inf[0] != 0.  shadow: a 16-bit
     buffer of param's length receiving the updated values (the trainer's bf16 shadow);
-    zero_grad: grad is zeroed in the same pass (also on a skipped step)."""
+    zero_grad: grad is zeroed in the same pass (also on a skipped step).  ema with ema_decay
+    (both or neither): a contiguous f32 buffer of param's length that takes
+    ``ema.lerp_(param, 1 - ema_decay)`` on the updated values in the same pass, untouched on a
+    skipped step; 0 <= ema_decay < 1 (trainer.ema_rule restates the arithmetic)."""
+    if (ema is None) != (ema_decay is None):
+        raise ValueError("adamw_dev_: ema and ema_decay go together")
+    if ema is not None:
+        _check_ema_decay("adamw_dev_", ema_decay)
+        if ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() != param.numel():
+            raise ValueError("adamw_dev_: ema must be a contiguous f32 buffer of the parameters' length")
+        if shadow is not None and (shadow.numel() != param.numel() or shadow.dtype not in _LOW):
+            raise ValueError("adamw_dev_: the shadow must be a 16-bit buffer of the parameters' length")
+        _need_cuda(param, ema)
+        _lib.call("msu_adamw_dev3", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(ema), param.numel(),
+                  _p(hyper), beta1, beta2, eps, weight_decay, float(ema_decay), _p(inv_scale), _p(found_inf),
+                  _p(shadow), _DT[shadow.dtype] if shadow is not None else 0, int(bool(zero_grad)), _s(param))
+        return
     _need_cuda(param)
     if shadow is None and not zero_grad:
         _lib.call("msu_adamw_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(hyper),
@@ -2176,6 +2192,32 @@ def adamw_dev_(param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2, eps, weigh
     _lib.call("msu_adamw_dev2", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(hyper),
               beta1, beta2, eps, weight_decay, _p(inv_scale), _p(found_inf), _p(shadow),
               _DT[shadow.dtype] if shadow is not None else 0, int(bool(zero_grad)), _s(param))
+
+
+def _check_ema_decay(who, decay):
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay < 1.0:
+        raise ValueError(f"{who}: ema_decay must be a number in [0, 1), got {decay!r}")
+
+
+def swap_cast_(a, b, shadow=None):
+    """(a, b) = (b, a) in place over two flat f32 buffers of one length, one launch; shadow (a
+    16-bit buffer of that length) receives the new a rounded as adamw_dev_ rounds it.  The buffers
+    must be contiguous, 16-byte aligned and must not overlap."""
+    for t in (a, b):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError("swap_cast_: a and b must be contiguous flat f32 buffers")
+    n = a.numel()
+    if b.numel() != n:
+        raise ValueError(f"swap_cast_: a has {n} elements, b {b.numel()}")
+    if shadow is not None and (shadow.numel() != n or shadow.dtype not in _LOW or not shadow.is_contiguous()):
+        raise ValueError("swap_cast_: the shadow must be a contiguous 16-bit buffer of a's length")
+    if any(t is not None and t.data_ptr() % 16 for t in (a, b, shadow)):
+        raise ValueError("swap_cast_: a, b and the shadow must be 16-byte aligned")
+    pa, pb = a.data_ptr(), b.data_ptr()
+    if pa < pb + 4 * n and pb < pa + 4 * n:
+        raise ValueError("swap_cast_: a and b overlap")
+    _need_cuda(a, b, shadow)
+    _lib.call("msu_swap_cast", pa, pb, _p(shadow), _DT[shadow.dtype] if shadow is not None else 0, n, _s(a))
 
 
 def step_advance_(hyper, found_inf=None):

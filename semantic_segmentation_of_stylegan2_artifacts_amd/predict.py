@@ -9,7 +9,9 @@ f32 probability map of every image copied to the host) and renders each map on t
 the BCE sum and the finished byte images; only ``[B, 12]`` doubles and bytes reach the host.
 
     python -m semantic_segmentation_of_stylegan2_artifacts_amd.predict --cfg FILE \\
-        --check_point_dir DIR --out_dir DIR [--batch_size N] [--no_labels]
+        --check_point_dir DIR --out_dir DIR [--batch_size N] [--no_labels] [--ema]
+
+(``--ema``: the averaged weights a checkpoint saved with ``ema_state=`` holds under ``"model_ema"``.)
 
 Not ported: the matplotlib figure with a colour bar that ``save_color_heatmap`` draws around
 the overlay (``{case}_heatmap.png`` holds the overlay array itself), tensorboard, tqdm, csv.
@@ -231,6 +233,8 @@ def main(argv=None):
     parser.add_argument("--out_dir", type=str, required=True, metavar="DIR", help="path to the out dir")
     parser.add_argument("--batch_size", type=int, default=None, help="images per forward (default DATA.BATCH_SIZE)")
     parser.add_argument("--no_labels", action="store_true", help="unlabelled split: maps only")
+    parser.add_argument("--ema", action="store_true",
+                        help="load the checkpoint's averaged weights ('model_ema') instead of 'model'")
     args = parser.parse_args(argv)
     config = load_config(args.cfg)
     if not torch.cuda.is_available():
@@ -245,7 +249,8 @@ def main(argv=None):
     shutil.copy(args.cfg, os.path.join(output_dir, "config_used.yaml"))
 
     model = MSUNet(config, img_size=config.DATA.IMG_SIZE, num_classes=config.MODEL.NUM_CLASSES)
-    msg = checkpoint.load_checkpoint(model, os.path.join(args.check_point_dir, "best_model.pth"), strict=True)
+    msg = checkpoint.load_checkpoint(model, os.path.join(args.check_point_dir, "best_model.pth"), strict=True,
+                                     use_ema=args.ema)
     print("loaded checkpoint", msg)
     model.to(device)
 

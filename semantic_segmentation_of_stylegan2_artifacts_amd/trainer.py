@@ -18,7 +18,8 @@ Here:
   into the fused AdamW kernel; ``grad_wire_dtype`` (bf16 / f16) all-reduces 16-bit casts of
   the buckets instead (half the bytes; BASELINE config 5's "fp16 grads");
 * AdamW = one fused HIP launch per group over the flat buffer, lr / step read from device
-  memory, skipped (GradScaler semantics) when a gradient is non-finite;
+  memory, skipped (GradScaler semantics) when a gradient is non-finite; ``ema_decay`` adds an
+  exponential moving average of the weights to that same launch, ``ema_scope()`` evaluates on it;
 * after four eager steps the device side of the step is captured into a HIP graph and
   replayed (``Trainer.step``) when the eager step is launch-bound: the host then issues one
   launch per step;
@@ -26,6 +27,7 @@ Here:
   receive gradients there; they are excluded here, matching torch AdamW's skip of
   ``grad is None``.
 """
+import contextlib
 import math
 import os
 import threading
@@ -82,6 +84,8 @@ class FlatGroup:
         # 16-bit shadow of the parameters (the trainer's compute dtype, bf16 or f16), refreshed
         # once per step: the Linear ops read it instead of casting every weight at every call
         self.shadow = torch.empty(n, device=device, dtype=shadow_dtype)
+        # the weights' exponential moving average (Trainer(ema_decay=...) allocates it): same layout
+        self.ema = None
         for p, off in zip(self.params, self.offsets):
             k = p.numel()
             self.data[off:off + k].copy_(p.detach().reshape(-1))
@@ -340,6 +344,24 @@ def grad_clip_rule(sumsq, inv, max_norm):
     return f32(norm), f32(inv * (coef if coef < 1.0 else 1.0))
 
 
+def ema_rule(ema, p, decay):
+    """Host restatement of the moving average ``msu_adamw_dev3`` keeps (ATen's
+    ``ema.lerp_(p, 1 - decay)``, timm ModelEmaV2's update): the new average from the old one and
+    the parameters just written, on numpy float32 (every operation rounds to f32, none fuses).
+    The weight 1 - decay is formed in double and rounded once.  ema / p: arrays or tensors; returns
+    a float32 numpy array."""
+    import numpy as np
+
+    def f32(t):
+        return t.detach().cpu().numpy().astype(np.float32) if torch.is_tensor(t) else np.asarray(t, dtype=np.float32)
+    e, p = f32(ema), f32(p)
+    w = np.float32(1.0 - float(decay))
+    with np.errstate(all="ignore"):
+        if w < np.float32(0.5):
+            return e + w * (p - e)
+        return p - (p - e) * (np.float32(1.0) - w)
+
+
 def reseed(seed, rank=0):
     """Per-rank randomness for data parallelism: the model is built from the shared seed
     (identical initial weights on every rank), then every rank draws its own drop-path and
@@ -373,11 +395,19 @@ def rccl_capture_blocker(process_group):
 
 
 class Trainer:
+    _ema_decay = None
+    _in_ema_scope = False  # True inside ema_scope(): the weights and their EMA are swapped
+
     def __init__(self, model, config, device, lr=None, amp_dtype=torch.bfloat16, bucket_mb=32,
                  world_size=1, process_group=None, rank=0, seed=None, skip_nonfinite=True, use_graph=None,
                  graph_warmup=4, grad_wire_dtype=None, always_reduce=False, loss_scale=None, init_scale=65536.0,
-                 growth_interval=2000, max_grad_norm=None):
+                 growth_interval=2000, max_grad_norm=None, ema_decay=None):
         self.model = model
+        # ema_decay: None (no moving average: nothing allocated, nothing launched) or a float in
+        # [0, 1): every applied AdamW step also moves a flat f32 average of the weights,
+        # ema.lerp_(p, 1 - decay), in the optimizer's own pass (timm ModelEmaV2's rule and start);
+        # ema_scope() evaluates on it
+        self._ema_decay = self._check_ema_decay(ema_decay)
         self.device = device
         self.amp_dtype = amp_dtype
         self.rank = rank
@@ -423,6 +453,9 @@ class Trainer:
         sdt = amp_dtype if self.amp16 else torch.bfloat16
         self.groups = [FlatGroup(decay[::-1], config.TRAIN.WEIGHT_DECAY, device, sdt),
                        FlatGroup(no_decay[::-1], 0.0, device, sdt)]
+        if self._ema_decay is not None:
+            for g in self.groups:  # the average starts as the weights; the alignment gaps stay zero
+                g.ema = g.data.clone()
         # the dead branches' parameters are never updated: one 16-bit shadow each for the run, so
         # their no-grad forwards (side stream) read it instead of casting every weight every step
         # (16 cast launches per step at Swin-T); a write through the parameter (load_state_dict)
@@ -537,6 +570,106 @@ class Trainer:
         if value != self._max_grad_norm:
             self.invalidate_graph()
         self._max_grad_norm = value
+
+    @staticmethod
+    def _check_ema_decay(value):
+        if value is None:
+            return None
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 <= value < 1.0:
+            raise ValueError(f"ema_decay must be None or a number in [0, 1), got {value!r}")
+        return float(value)
+
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        """A launch argument of the captured step, like the betas: the graph is dropped when it
+        changes.  The average's buffers are chosen at construction."""
+        value = self._check_ema_decay(value)
+        if (value is None) != (self._ema_decay is None):
+            raise ValueError("the weight EMA is switched on or off at construction (ema_decay=...)")
+        if value != self._ema_decay:
+            self.invalidate_graph()
+        self._ema_decay = value
+
+    def _need_ema(self, what):
+        if self._ema_decay is None:
+            raise RuntimeError(f"{what}: this trainer keeps no weight EMA (Trainer(ema_decay=...))")
+        if self._in_ema_scope:
+            raise RuntimeError(f"{what}: not inside ema_scope() (the weights and their EMA are swapped)")
+
+    def ema_scope(self):
+        """Evaluate on the averaged weights: ``with tr.ema_scope(): validation.evaluate(...)``.
+
+        On entry each group's weights and their EMA change places in one launch that also re-emits
+        the 16-bit shadow (then the transposed shadow); the exit does the same again, which restores
+        every buffer bitwise, also when the body raises.  The swap writes through raw pointers:
+        parameter versions do not move, the Linear ops keep reading the shadows, and the pointers
+        a captured step holds stay valid.  Inside, step() and a nested ema_scope() raise."""
+        self._need_ema("ema_scope")  # raises here, not only on entry
+        return self._ema_scope()
+
+    @contextlib.contextmanager
+    def _ema_scope(self):
+        self._need_ema("ema_scope")
+        self._swap_ema()
+        self._in_ema_scope = True
+        try:
+            yield self
+        finally:
+            self._in_ema_scope = False
+            self._swap_ema()
+
+    def _swap_ema(self):
+        for g in self.groups:
+            ops.swap_cast_(g.data, g.ema, g.shadow if self.amp16 else None)
+            if self.amp16:
+                g.transpose_shadow()
+
+    def _owned(self):
+        """state-dict key -> (group, offset, parameter) of every parameter this trainer updates
+        (a parameter registered under two names has both keys)."""
+        where = {id(p): (g, off, p) for g in self.groups for p, off in zip(g.params, g.offsets)}
+        return {k: where[id(p)] for k, p in self.model.named_parameters(remove_duplicate=False) if id(p) in where}
+
+    def ema_state_dict(self):
+        """The model's ``state_dict()`` on the CPU with every parameter this trainer owns replaced
+        by its EMA; the rest (dead-branch parameters, buffers) as the model has it.  Loads into a
+        model like any state dict."""
+        self._need_ema("ema_state_dict")
+        owned = self._owned()
+        sd = {}
+        for k, t in self.model.state_dict().items():
+            if k in owned:
+                g, off, p = owned[k]
+                t = g.ema[off:off + p.numel()].view_as(p)
+            sd[k] = t.detach().cpu().clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """Inverse of ema_state_dict: the owned parameters' entries of ``sd`` become the EMA (a
+        missing key or a wrong shape among them raises; other entries are ignored).  The model's
+        weights do not move."""
+        self._need_ema("load_ema_state_dict")
+        owned = self._owned()
+        missing = [k for k in owned if k not in sd]
+        if missing:
+            raise KeyError(f"EMA state lacks {len(missing)} owned parameters, e.g. {missing[:3]}")
+        bad = [k for k, (_, _, p) in owned.items() if tuple(sd[k].shape) != tuple(p.shape)]
+        if bad:
+            raise ValueError(f"EMA state has wrong shapes for {bad[:3]}: "
+                             f"{[tuple(sd[k].shape) for k in bad[:3]]} vs {[tuple(owned[k][2].shape) for k in bad[:3]]}")
+        for k, (g, off, p) in owned.items():
+            g.ema[off:off + p.numel()].copy_(sd[k].detach().reshape(-1))
+
+    def reset_ema(self):
+        """Restart the EMA from the current weights.  ``model.load_state_dict`` writes the weights
+        only and does not move the EMA: call this after loading weights into a built trainer."""
+        self._need_ema("reset_ema")
+        for g in self.groups:
+            g.ema.copy_(g.data)
 
     def grad_norm(self):
         """The last step's global gradient norm, of exactly what AdamW consumed (reduced,
@@ -669,6 +802,8 @@ class Trainer:
         captured once into a HIP graph and replayed: one launch per step instead of ~1300.
         Inputs are copied into the graph's static buffers; dropout keeps drawing fresh masks
         (device-side seed counter, drop-path pools redrawn inside the graph)."""
+        if self._in_ema_scope:
+            raise RuntimeError("step() inside ema_scope(): the weights and their EMA are swapped")
         if not self.model.training:  # Module.train() walks all ~400 modules: ~1 ms of host time
             self.model.train()
         if self.graph_mode == "auto" and self.step_count >= self.graph_warmup and self._graph is None:
@@ -744,10 +879,11 @@ class Trainer:
         for g in self.groups:
             # the gradient reset and (16-bit) the shadow refresh ride in AdamW's pass: no fill and
             # no re-read of the parameters for the cast (a skipped step leaves the shadow as is
-            # and zeroes the gradient too)
+            # and zeroes the gradient too); so does the weight EMA, which a skipped step leaves alone
+            ema = {} if self._ema_decay is None else {"ema": g.ema, "ema_decay": self._ema_decay}
             ops.adamw_dev_(g.data, g.grad, g.exp_avg, g.exp_avg_sq, self.hyper, self.betas[0], self.betas[1],
                            self.eps, g.weight_decay, inv_scale=inv, found_inf=found,
-                           shadow=g.shadow if amp16 else None, zero_grad=True)
+                           shadow=g.shadow if amp16 else None, zero_grad=True, **ema)
             if amp16:  # keeps evaluation between steps on the updated weights
                 g.transpose_shadow()
         return loss.detach()
@@ -794,6 +930,8 @@ class Trainer:
 
     def _capture(self, images, labels):
         """Capture _device_step into a HIP graph (nothing executes during capture)."""
+        if self._in_ema_scope:
+            raise RuntimeError("cannot capture the training step inside ema_scope()")
         blocker = rccl_capture_blocker(self.reducer.pg) if self.reducer is not None else None
         if blocker:  # use_graph forced on after construction: refuse instead of aborting later
             raise RuntimeError(f"cannot capture the training step: {blocker}")
