@@ -483,6 +483,17 @@ int msu_conv3x3_weight(int dtype, const float* W, void* out, int Cout, int Cin, 
 int msu_augment_batch(const unsigned char* img, const unsigned char* label, const int* ops,
                       const unsigned char* luts, float* out, float* out_label, int B, int H, int W,
                       void* stream);
+/* msu_augment_batch over a resident store of decoded samples (the device sample cache,
+ * dataset/cache.py): output sample b is built from source row rows[b].  img_rows [n_rows, H, W, 3]
+ * u8, label_rows [n_rows, H, W] u8 or null; rows [B] i32 on the device, uniform per workgroup and
+ * clamped into [0, n_rows) by the kernel (it never reads outside the store; valid indices are the
+ * caller's job), every source offset 64-bit; ops, luts, out, out_label as above.  At 1024^2 a
+ * stored sample is 3 MiB + 1 MiB.  -2, nothing launched: B, H, W or n_rows <= 0; img_rows, rows or
+ * out null; label_rows / out_label not both or neither; ops without luts; B or ceil(H / 16) above
+ * 65535; n_rows * H * W * 3 or B * H * W * 3 >= 2^40. */
+int msu_augment_gather(const unsigned char* img_rows, const unsigned char* label_rows, const int* rows,
+                       int n_rows, const int* ops, const unsigned char* luts, float* out, float* out_label,
+                       int B, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,7 @@ SIGNATURES = {
     "msu_metrics_nblk": (I, [L]),
     "msu_seg_metrics": (I, [I, P, P, I, L, F, P, I, P, P]),
     "msu_augment_batch": (I, [P, P, P, P, P, P, I, I, I, P]),
+    "msu_augment_gather": (I, [P, P, P, I, P, P, P, P, I, I, I, P]),
     "msu_pred_maps_nblk": (I, [I, I]),
     "msu_pred_maps": (I, [I, P, P, P, I, I, I, F, F, F, F, I, I, P, P, P, P, P, P, P, P]),
 }

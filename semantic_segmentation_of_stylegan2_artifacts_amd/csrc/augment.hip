@@ -21,6 +21,8 @@
 // HBM-bound: 4 B read + 16 B written per pixel.  One workgroup = a 64 x 16 output tile of one
 // sample; the point-wise chain runs once per source pixel (halo included when the sample
 // blurs) into an LDS tile that the blur and the flipped, planar float4 stores read.
+// msu_augment_gather is the same kernel body over a resident store of decoded samples
+// (dataset/cache.py): sample b reads source row rows[b], so a step uploads indices, not pixels.
 #pragma clang fp contract(off)  // the HSV f32 formula must round like cv2's scalar code
 #include "common.h"
 
@@ -96,13 +98,20 @@ struct AugShared {
 
 MSU_DEV int chan(uint32_t p, int c) { return (int)((p >> (8 * c)) & 0xffu); }
 
+// GATHER: output sample b is built from source row rows[b] of a resident [n_rows, H, W, 3] /
+// [n_rows, H, W] store (the device sample cache) instead of from sample b of the batch.  The index
+// is uniform per workgroup (one scalar load), clamped into [0, n_rows) so that no value of it
+// reads outside the store, and widened before it is scaled: a store of 1957 rows of 1024^2 is 6 GB.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lbl,
+                                                      const int* __restrict__ rows, int n_rows,
                                                       const int* __restrict__ ops, const uint8_t* __restrict__ luts,
                                                       float* __restrict__ out, float* __restrict__ out_lbl, int H,
                                                       int W) {
   __shared__ AugShared sh;
   const int t = threadIdx.x;
   const int b = blockIdx.z;
+  const long srow = GATHER ? (long)min(max(rows[b], 0), n_rows - 1) : (long)b;
   const int op = ops ? ops[2 * b] : 0;
   const int ks = ops ? ops[2 * b + 1] : 0;
   const bool flip = (op & OP_FLIP) != 0;
@@ -122,10 +131,10 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
   // tile column c <-> source column sx0 + c; output column = flip ? W-1-(sx0+c) : sx0+c
   const int sx0 = flip ? W - ox0 - TW : ox0;
   const long plane = (long)H * W;
-  const uint8_t* src = img + (long)b * plane * 3;
+  const uint8_t* src = img + srow * plane * 3;
   const int halo = ks > 0 ? HR : 0;
-  const int rows = TH + 2 * halo, cols = TW + 2 * halo;
-  for (int i = t; i < rows * cols; i += 256) {
+  const int trows = TH + 2 * halo, cols = TW + 2 * halo;
+  for (int i = t; i < trows * cols; i += 256) {
     const int ty = i / cols, tx = i - ty * cols;
     const int sy = reflect101(oy0 - halo + ty, H), sx = reflect101(sx0 - halo + tx, W);
     const uint8_t* p = src + ((long)sy * W + sx) * 3;
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
     }
   }
   if (lbl) {
-    const uint8_t* l = lbl + (long)b * plane + (long)oy * W;
+    const uint8_t* l = lbl + srow * plane + (long)oy * W;
     float* ol = out_lbl + (long)b * plane + (long)oy * W;
     float lv[4];
 #pragma unroll
@@ -239,8 +248,26 @@ int msu_augment_batch(const unsigned char* img, const unsigned char* label, cons
   if ((long)B * H * W * 3 >= (1L << 40)) return -2;
   const dim3 grid((unsigned)((W + TW - 1) / TW), (unsigned)((H + TH - 1) / TH), (unsigned)B);
   if (grid.z > 65535u || grid.y > 65535u) return -2;
-  hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, (hipStream_t)stream, img, label, ops, luts, out,
-                     out_label, H, W);
+  hipLaunchKernelGGL(augment_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, img, label, nullptr, 0, ops,
+                     luts, out, out_label, H, W);
+  return MSU_CHECK_LAUNCH();
+}
+
+// msu_augment_batch reading its B samples from rows[b] of img_rows [n_rows, H, W, 3] u8 /
+// label_rows [n_rows, H, W] u8 (or null); rows [B] i32 on the device, clamped into [0, n_rows).
+int msu_augment_gather(const unsigned char* img_rows, const unsigned char* label_rows, const int* rows,
+                       int n_rows, const int* ops, const unsigned char* luts, float* out, float* out_label,
+                       int B, int H, int W, void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || n_rows <= 0 || !img_rows || !rows || !out) return -2;
+  if ((label_rows == nullptr) != (out_label == nullptr)) return -2;
+  if (ops && !luts) return -2;
+  const long sample = (long)H * W * 3;  // < 2^63: H, W < 2^31
+  const long lim = 1L << 40;
+  if (sample >= lim || (long)n_rows > (lim - 1) / sample || (long)B > (lim - 1) / sample) return -2;
+  const dim3 grid((unsigned)((W + TW - 1) / TW), (unsigned)((H + TH - 1) / TH), (unsigned)B);
+  if (grid.z > 65535u || grid.y > 65535u) return -2;
+  hipLaunchKernelGGL(augment_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, img_rows, label_rows, rows,
+                     n_rows, ops, luts, out, out_label, H, W);
   return MSU_CHECK_LAUNCH();
 }
 

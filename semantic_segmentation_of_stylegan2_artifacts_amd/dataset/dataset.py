@@ -63,6 +63,62 @@ def augment_batch(img_u8, lbl_u8, ops=None, luts=None):
     return out, out_l
 
 
+def augment_gather(img_rows, lbl_rows, rows, ops=None, luts=None):
+    """``augment_batch`` over a resident store (``DeviceSampleCache``): img_rows [n_rows, H, W, 3]
+    u8 and lbl_rows [n_rows, H, W] u8 or None on the device, ``rows`` a host sequence or CPU int
+    tensor of B indices; output sample b is built from row ``rows[b]``.  The indices are checked
+    against ``n_rows`` on the host (ValueError) and only then uploaded; ops / luts and the result
+    are ``augment_batch``'s, launched on the current stream of img_rows' device."""
+    if img_rows.dtype != torch.uint8 or img_rows.dim() != 4 or img_rows.shape[-1] != 3:
+        raise ValueError(f"image rows must be uint8 [n_rows, H, W, 3], got {tuple(img_rows.shape)} {img_rows.dtype}")
+    n_rows, H, W, _ = img_rows.shape
+    dev = img_rows.device
+    if not img_rows.is_contiguous():
+        raise ValueError("image rows must be contiguous (the store is not copied)")
+    if lbl_rows is not None:
+        if lbl_rows.dtype != torch.uint8 or tuple(lbl_rows.shape) != (n_rows, H, W):
+            raise ValueError(f"label rows must be uint8 [n_rows, H, W] = {(n_rows, H, W)}, got {tuple(lbl_rows.shape)}")
+        if lbl_rows.device != dev or not lbl_rows.is_contiguous():
+            raise ValueError("label rows must be contiguous and on the image rows' device")
+    if isinstance(rows, torch.Tensor):
+        if rows.is_cuda or rows.dim() != 1 or rows.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
+            raise ValueError(f"rows must be a host sequence or a 1-d CPU int tensor, got {tuple(rows.shape)} "
+                             f"{rows.dtype} on {rows.device}")
+        rows_h = rows
+    else:
+        rows_h = torch.as_tensor(np.asarray(list(rows)))
+        if rows_h.dim() != 1 or rows_h.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"rows must be a sequence of ints, got {tuple(rows_h.shape)} {rows_h.dtype}")
+    B = rows_h.numel()
+    if B == 0:
+        raise ValueError("rows is empty")
+    lo, hi = int(rows_h.min()), int(rows_h.max())
+    if lo < 0 or hi >= n_rows:
+        raise ValueError(f"row index {lo if lo < 0 else hi} outside the store's [0, {n_rows})")
+    if (ops is None) != (luts is None):
+        raise ValueError("ops and luts go together")
+    if ops is not None:
+        if tuple(ops.shape) != (B, 2) or ops.dtype != torch.int32:
+            raise ValueError(f"ops must be int32 [B, 2], got {tuple(ops.shape)} {ops.dtype}")
+        if tuple(luts.shape) != (B, augment.N_LUT, 256) or luts.dtype != torch.uint8:
+            raise ValueError(f"luts must be uint8 [B, 5, 256], got {tuple(luts.shape)} {luts.dtype}")
+        if ops.device != dev or luts.device != dev:
+            raise ValueError("ops and luts must be on the image rows' device")
+        ops, luts = ops.contiguous(), luts.contiguous()
+    if not img_rows.is_cuda:
+        raise RuntimeError("augment_gather needs the sample rows on a HIP device (no CPU fallback)")
+    rows_d = rows_h.to(torch.int32).contiguous().to(dev, non_blocking=True)
+    out = torch.empty(B, 3, H, W, device=dev, dtype=torch.float32)
+    out_l = None if lbl_rows is None else torch.empty(B, H, W, device=dev, dtype=torch.float32)
+
+    def p(t):
+        return None if t is None else t.data_ptr()
+
+    _lib.call("msu_augment_gather", p(img_rows), p(lbl_rows), p(rows_d), n_rows, p(ops), p(luts), p(out), p(out_l),
+              B, H, W, torch._C._cuda_getCurrentRawStream(dev.index))
+    return out, out_l
+
+
 def _device():
     return torch.device("cuda", torch.cuda.current_device())
 

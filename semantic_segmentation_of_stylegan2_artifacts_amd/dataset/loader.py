@@ -16,7 +16,9 @@ draws every sample's augmentation on the host (``dataset.augment``, keyed by (se
 index)), copies the slot to the device on its own stream and launches ``msu_augment_batch``
 there; the consumer's stream waits on an event, so decode, upload and augmentation of the
 next step overlap the current training step.  ``slots`` pinned slots rotate; a slot is reused
-only after its upload has completed.
+only after its upload has completed.  With ``cache=`` (``dataset.cache.DeviceSampleCache``)
+only the samples the cache does not hold are decoded and uploaded, into their cache rows, and
+``msu_augment_gather`` builds the batch from the cache; the stream is then the cache's.
 
 Data parallel: each step consumes ``batches_per_step * world_size`` consecutive sampler
 batches; rank r takes the ``batches_per_step`` batches of slice r (the reference's sampler
@@ -32,7 +34,7 @@ from torch.utils.data import ConcatDataset, Subset
 
 from ..scripts.batch_data_loader_V2 import BatchPatternSampler
 from . import augment
-from .dataset import DataPrepartion, RandomGenerator, augment_batch
+from .dataset import DataPrepartion, RandomGenerator, augment_batch, augment_gather
 
 
 # ------------------------------------------------------------------ epoch plan (trainer.py:195-237)
@@ -107,11 +109,13 @@ def _base_transform(ds):
 
 
 class _Slot:
-    def __init__(self, B, H, W, labels):
+    def __init__(self, B, H, W, labels, rows=False):
         self.img = torch.empty(B, H, W, 3, dtype=torch.uint8).pin_memory()
         self.lbl = torch.empty(B, H, W, dtype=torch.uint8).pin_memory() if labels else None
         self.ops = torch.empty(B, 2, dtype=torch.int32).pin_memory()
         self.luts = torch.empty(B, augment.N_LUT, 256, dtype=torch.uint8).pin_memory()
+        # cache rows of the step's samples (cached loader only)
+        self.rows = torch.empty(B, dtype=torch.int32).pin_memory() if rows else None
         self.uploaded = None  # event: the slot's H2D copies are done
 
 
@@ -121,10 +125,18 @@ class GpuBatchLoader:
     Subset / ConcatDataset) and a batch sampler.
 
     ``transform``: a ``RandomGenerator`` / ``DataPrepartion`` (default: the dataset's own, else
-    normalisation only); ``seed`` / ``epoch`` key the per-sample draws."""
+    normalisation only); ``seed`` / ``epoch`` key the per-sample draws.
+
+    ``cache``: a ``DeviceSampleCache``.  Each step then decodes only the samples the cache does
+    not hold yet, copies them into their rows (or, once the cache is full, into this slot's share
+    of the staging rows) and launches ``msu_augment_gather`` over the cache; the draws, and so the
+    batches, are bitwise those of the uncached loader.  The loader works on the cache's stream
+    (``stream``: one to bring along; refused with ``RuntimeError`` when the cache already has
+    another), so one cache can serve the loaders of successive epochs."""
 
     def __init__(self, dataset, batch_sampler, *, transform=None, device=None, num_threads=8, slots=3,
-                 seed=1234, epoch=0, rank=0, world_size=1, batches_per_step=1, drop_last=True):
+                 seed=1234, epoch=0, rank=0, world_size=1, batches_per_step=1, drop_last=True, cache=None,
+                 stream=None):
         self.dataset = dataset
         self.batch_sampler = batch_sampler
         self.transform = transform if transform is not None else _base_transform(dataset)
@@ -137,6 +149,15 @@ class GpuBatchLoader:
         self.drop_last = drop_last
         self._slots = None
         self._stream = None
+        self.cache = cache
+        if cache is not None:
+            a, b = cache.device, self.device
+            if a.type != b.type or (a.index is not None and b.index is not None and a.index != b.index):
+                raise ValueError(f"cache on {a}, loader on {b}")
+            self.device = a
+            self._stream = cache.attach(stream)
+        elif stream is not None:
+            raise ValueError("stream= goes with cache=: the uncached loader owns its stream")
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -184,7 +205,42 @@ class GpuBatchLoader:
             pool.shutdown(wait=True)
         q.put(None)
 
+    def _load_step_cached(self, pool, q, k, idx):
+        """``_load_step`` through ``self.cache``: only the misses are decoded and uploaded."""
+        cache, B = self.cache, len(idx)
+        refs = [resolve(self.dataset, i) for i in idx]
+        if self._slots is None:
+            self._slots = [_Slot(B, cache.H, cache.W, cache.labels, rows=True) for _ in range(self.n_slots)]
+        s = k % self.n_slots
+        slot = self._slots[s]
+        if slot.uploaded is not None:
+            slot.uploaded.synchronize()
+        if B > slot.img.shape[0]:
+            raise ValueError(f"step of {B} samples exceeds the slot size {slot.img.shape[0]}")
+        per_slot = cache.staging // self.n_slots  # this slot's staging rows
+        check = self.transform.check if self.transform is not None else None
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            rows = cache.load(refs, slot.img, slot.lbl, staging_offset=s * per_slot, staging_count=per_slot,
+                              pool=pool, check=check)
+            for j in range(B):
+                op, ks, luts = self._draw(idx[j])
+                slot.ops[j, 0], slot.ops[j, 1] = op, ks
+                slot.luts[j] = torch.from_numpy(luts)
+                slot.rows[j] = rows[j]
+            ops_d = slot.ops[:B].to(self.device, non_blocking=True)
+            luts_d = slot.luts[:B].to(self.device, non_blocking=True)
+            x, y = augment_gather(cache.img, cache.lbl, slot.rows[:B], ops_d, luts_d)
+            # the row indices go up inside augment_gather, so the slot's event follows the launch
+            slot.uploaded = torch.cuda.Event()
+            slot.uploaded.record(self._stream)
+            done = torch.cuda.Event()
+            done.record(self._stream)
+        names = [ds.sample_list[i].strip('\n') for ds, i in refs]
+        q.put((x, y, names, done))
+
     def _load_step(self, pool, q, k, idx):
+        if self.cache is not None:
+            return self._load_step_cached(pool, q, k, idx)
         B = len(idx)
         refs = [resolve(self.dataset, i) for i in idx]
         first = refs[0][0].read_raw(refs[0][1]) if self._slots is None else None

@@ -9,7 +9,7 @@ f32 probability map of every image copied to the host) and renders each map on t
 the BCE sum and the finished byte images; only ``[B, 12]`` doubles and bytes reach the host.
 
     python -m semantic_segmentation_of_stylegan2_artifacts_amd.predict --cfg FILE \\
-        --check_point_dir DIR --out_dir DIR [--batch_size N] [--no_labels] [--ema]
+        --check_point_dir DIR --out_dir DIR [--batch_size N] [--no_labels] [--ema] [--cache]
 
 (``--ema``: the averaged weights a checkpoint saved with ``ema_state=`` holds under ``"model_ema"``.)
 
@@ -192,10 +192,42 @@ def save_maps(case_name, maps, out_dir, image_u8=None):
     return paths
 
 
-def dataset_batches(dataset, batch_size, device):
+def _cached_batches(dataset, batch_size, device, cache):
+    """``dataset_batches`` through a ``DeviceSampleCache``: a file is decoded the first time it
+    is met (every time once the cache is full) and later passes gather its row on the device.
+    Fills and gathers run on the cache's stream; the caller's stream waits for each batch."""
+    from .dataset.dataset import augment_gather
+    n = len(dataset)
+    stream = cache.attach()
+    pin = torch.empty(batch_size, cache.H, cache.W, 3, dtype=torch.uint8).pin_memory()
+    pin_l = torch.empty(batch_size, cache.H, cache.W, dtype=torch.uint8).pin_memory() if cache.labels else None
+    uploaded = None
+    for i0 in range(0, n, batch_size):
+        idx = range(i0, min(n, i0 + batch_size))
+        if uploaded is not None:
+            uploaded.synchronize()  # the pinned rows are free again
+        with torch.cuda.device(device), torch.cuda.stream(stream):
+            rows = cache.load([(dataset, i) for i in idx], pin, pin_l, staging_count=min(cache.staging, batch_size))
+            uploaded = torch.cuda.Event()
+            uploaded.record(stream)
+            x, y = augment_gather(cache.img, cache.lbl, rows)
+        cur = torch.cuda.current_stream(device)
+        cur.wait_stream(stream)
+        x.record_stream(cur)
+        if y is not None:
+            y.record_stream(cur)
+        yield x, y, [dataset.sample_list[i].strip("\n") for i in idx]
+
+
+def dataset_batches(dataset, batch_size, device, cache=None):
     """``(images, labels, case_names)`` batches of a ``SegArtifact_dataset`` /
     ``SegArtifact_no_label_dataset`` in list order, no augmentation: PIL decode on the host,
-    /255, label threshold and HWC -> CHW in ``msu_augment_batch`` on the GPU."""
+    /255, label threshold and HWC -> CHW in ``msu_augment_batch`` on the GPU.  ``cache``: a
+    ``dataset.DeviceSampleCache``; the split is then decoded once and later passes (validation
+    after every epoch) gather it from the device with ``msu_augment_gather``, same bytes."""
+    if cache is not None:
+        yield from _cached_batches(dataset, batch_size, device, cache)
+        return
     from .dataset.dataset import augment_batch
     n = len(dataset)
     for i0 in range(0, n, batch_size):
@@ -235,6 +267,9 @@ def main(argv=None):
     parser.add_argument("--no_labels", action="store_true", help="unlabelled split: maps only")
     parser.add_argument("--ema", action="store_true",
                         help="load the checkpoint's averaged weights ('model_ema') instead of 'model'")
+    parser.add_argument("--cache", action="store_true",
+                        help="keep the decoded split on the device (DeviceSampleCache, 4 B / pixel): the path "
+                             "a training loop's per-epoch validation takes; one pass here decodes as much")
     args = parser.parse_args(argv)
     config = load_config(args.cfg)
     if not torch.cuda.is_available():
@@ -258,7 +293,12 @@ def main(argv=None):
     db_test = cls(base_dir=config.DATA.DATA_PATH, list_dir=config.get("LIST_DIR", "./lists"), split="test",
                   transform=None)
     batch_size = int(args.batch_size or config.DATA.BATCH_SIZE)
-    res = test_split(model, dataset_batches(db_test, batch_size, device),
+    cache = None
+    if args.cache:
+        from .dataset import DeviceSampleCache
+        cache = DeviceSampleCache(config.DATA.IMG_SIZE, config.DATA.IMG_SIZE, labels=not args.no_labels,
+                                  device=device, max_samples=len(db_test))
+    res = test_split(model, dataset_batches(db_test, batch_size, device, cache=cache),
                      (config.TRAIN.TVERSKY_LOSS_ALPHA, config.TRAIN.TVERSKY_LOSS_BETA,
                       config.TRAIN.LOSS_TVERSKY_BCE_MIX),
                      threshold=config.TRAIN.SIG_THRESHOLD, amp_dtype=torch.float16,
