@@ -353,6 +353,19 @@ int msu_dynloss_bwd2(int dtype, const void* logits, const float* target, const f
 int msu_dynloss_fwd3(int dtype, const void* logits, const float* target, int B, long N,
                      float alpha, float beta, float mix, float* part, int nblk, float* loss, float* flag,
                      float* coef, float* zero_out, void* stream);
+/* The loss forms of a gradient-accumulation window (Trainer(accum_steps=k)): micro-batch i of the
+ * window carries the weight w = B_i / n.  fwd4 is fwd3 whose final launch also folds the loss into
+ * the window's, acc[0] = first ? w * loss[0] : acc[0] + w * loss[0] (one f32 multiply, one f32
+ * add), and writes zero_out only when first != 0; acc NULL: fwd3 exactly (w and first unused
+ * beyond the checks).  -2 before any launch: w not finite or <= 0, first outside {0, 1}, B outside
+ * 1..64.  bwd3 is bwd2 with the seed gs = gout ? gout[0] * w : w (one f32 multiply; w = 1: bwd2
+ * bitwise): the weight is a launch argument, the seed stays the device-side loss scale. */
+int msu_dynloss_fwd4(int dtype, const void* logits, const float* target, int B, long N,
+                     float alpha, float beta, float mix, float* part, int nblk, float* loss, float* flag,
+                     float* coef, float* zero_out, float* acc, float w, int first, void* stream);
+int msu_dynloss_bwd3(int dtype, const void* logits, const float* target, const float* coef,
+                     const float* flag, const float* gout, float w, int B, long N, float alpha, float beta,
+                     float mix, float* dlogits, void* stream);
 
 /* Validation metrics (scripts/validation_functions.py:37-309): per image, p = sigmoid(logit),
  * pred_bin = p > threshold (:106-107), gt = label > 0 (:108).  out [B][12] f64 = sum(p g),

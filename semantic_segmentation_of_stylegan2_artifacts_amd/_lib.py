@@ -57,6 +57,8 @@ SIGNATURES = {
     "msu_dynloss_fwd2": (I, [I, P, P, I, L, F, F, F, P, I, P, P, P, P]),
     "msu_dynloss_fwd3": (I, [I, P, P, I, L, F, F, F, P, I, P, P, P, P, P]),
     "msu_dynloss_bwd2": (I, [I, P, P, P, P, P, I, L, F, F, F, P, P]),
+    "msu_dynloss_fwd4": (I, [I, P, P, I, L, F, F, F, P, I, P, P, P, P, P, F, I, P]),
+    "msu_dynloss_bwd3": (I, [I, P, P, P, P, P, F, I, L, F, F, F, P, P]),
     "msu_adamw": (I, [P, P, P, P, L, F, F, F, F, F, I, P, P, P]),
     "msu_nonfinite": (I, [P, L, P, P]),
     "msu_nonfinite2": (I, [P, L, P, L, P, P]),

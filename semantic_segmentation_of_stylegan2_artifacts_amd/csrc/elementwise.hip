@@ -135,7 +135,8 @@ MSU_DEV double wave_sum_d(double v) {
 __global__ void __launch_bounds__(512) dynloss_final_kernel(const float* part, int B, int nblk, long N,
                                                             float alpha, float beta, float mix,
                                                             float smooth, float* loss, float* flag,
-                                                            float* coef, float* zero_out) {
+                                                            float* coef, float* zero_out, float* acc, float w,
+                                                            int first) {
   __shared__ int binarise;
   __shared__ double sums[64][5];  // B <= 64
   __shared__ float wmax[8];
@@ -180,21 +181,31 @@ __global__ void __launch_bounds__(512) dynloss_final_kernel(const float* part, i
         c[1] = 0.f; c[2] = 1.f; c[3] = 1.f;
       }
     }
-    loss[0] = (float)(total / B);
+    const float l = (float)(total / B);
+    loss[0] = l;
     flag[0] = (float)binarise;
-    if (zero_out) zero_out[0] = 0.f;  // the trainer's non-finite flag, reset for this step
+    // the trainer's non-finite flag, reset for this step (an accumulation window: by its first
+    // micro-batch only)
+    if (zero_out && first) zero_out[0] = 0.f;
+    if (acc) {
+      // the window's weighted mean: one f32 multiply, one f32 add, never contracted into an fma
+      const float t = __fmul_rn(w, l);
+      acc[0] = first ? t : __fadd_rn(acc[0], t);
+    }
   }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(256) dynloss_bwd_kernel(const T* logits, const float* target,
                                                           const float* coef, const float* flag,
-                                                          const float* gout, long N, int B,
+                                                          const float* gout, float w, long N, int B,
                                                           float alpha, float beta, float mix,
                                                           float* dlogits) {
   const long total = N * B;
   const bool bin = flag[0] != 0.f;
-  const float g = gout ? gout[0] / B : 1.f / B;
+  // w: the micro-batch's share of an accumulation window (1: a plain step, x * 1.f is exact)
+  const float gs = gout ? __fmul_rn(gout[0], w) : w;
+  const float g = gs / B;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int b = (int)(i / N);
     const float* c = coef + 4 * b;
@@ -488,7 +499,24 @@ int msu_dynloss_fwd3(int dtype, const void* logits, const float* target, int B, 
                                             (const T*)logits, target, N, nblk, part));
   if (B > 64) return -2;
   hipLaunchKernelGGL(dynloss_final_kernel, dim3(1), dim3(512), 0, st, part, B, nblk, N, alpha, beta,
-                     mix, 1e-6f, loss, flag, coef, zero_out);
+                     mix, 1e-6f, loss, flag, coef, zero_out, (float*)nullptr, 1.f, 1);
+  return MSU_CHECK_LAUNCH();
+}
+
+// fwd3 for one micro-batch of a gradient-accumulation window: the final launch also folds the
+// micro-batch's loss into the window's, acc[0] = first ? w * loss : acc[0] + w * loss (f32, one
+// multiply and one add), and resets zero_out only when first.  acc null: fwd3 exactly (zero_out
+// always reset).  Every refusal comes before the first launch.
+int msu_dynloss_fwd4(int dtype, const void* logits, const float* target, int B, long N,
+                     float alpha, float beta, float mix, float* part, int nblk, float* loss, float* flag,
+                     float* coef, float* zero_out, float* acc, float w, int first, void* stream) {
+  // (the comparisons are false for a NaN; 3.4028235e38f is FLT_MAX)
+  if (!(w > 0.f && w <= 3.4028235e38f) || (first != 0 && first != 1) || B < 1 || B > 64) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  MSU_DISPATCH(dtype, T, hipLaunchKernelGGL(dynloss_partial_kernel<T>, dim3(nblk, B), dim3(256), 0, st,
+                                            (const T*)logits, target, N, nblk, part));
+  hipLaunchKernelGGL(dynloss_final_kernel, dim3(1), dim3(512), 0, st, part, B, nblk, N, alpha, beta,
+                     mix, 1e-6f, loss, flag, coef, zero_out, acc, w, acc ? first : 1);
   return MSU_CHECK_LAUNCH();
 }
 
@@ -506,15 +534,23 @@ int msu_dynloss_fwd(int dtype, const void* logits, const float* target, int B, l
   return msu_dynloss_fwd2(dtype, logits, target, B, N, alpha, beta, mix, part, nblk, loss, loss + 1, coef, stream);
 }
 
-int msu_dynloss_bwd2(int dtype, const void* logits, const float* target, const float* coef,
-                     const float* flag, const float* gout, int B, long N, float alpha, float beta,
+// bwd2 with the seed weighted by w, a micro-batch's share of its window: gs = gout ? gout[0] * w : w
+// (one f32 multiply), then g = gs / B as before; w == 1 is bwd2 bitwise
+int msu_dynloss_bwd3(int dtype, const void* logits, const float* target, const float* coef,
+                     const float* flag, const float* gout, float w, int B, long N, float alpha, float beta,
                      float mix, float* dlogits, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)B * N;
   MSU_DISPATCH(dtype, T, hipLaunchKernelGGL(dynloss_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st,
-                                            (const T*)logits, target, coef, flag, gout, N, B, alpha, beta, mix,
-                                            dlogits));
+                                            (const T*)logits, target, coef, flag, gout, w, N, B, alpha, beta,
+                                            mix, dlogits));
   return MSU_CHECK_LAUNCH();
+}
+
+int msu_dynloss_bwd2(int dtype, const void* logits, const float* target, const float* coef,
+                     const float* flag, const float* gout, int B, long N, float alpha, float beta,
+                     float mix, float* dlogits, void* stream) {
+  return msu_dynloss_bwd3(dtype, logits, target, coef, flag, gout, 1.f, B, N, alpha, beta, mix, dlogits, stream);
 }
 
 int msu_dynloss_bwd(int dtype, const void* logits, const float* target, const float* coef,

@@ -1945,6 +1945,33 @@ def step_flag_reset():
     return _step_flag[1]
 
 
+# The loss accumulator of a gradient-accumulation window (Trainer(accum_steps=k)): while one is
+# registered the DynamicLoss forward runs msu_dynloss_fwd4 (acc = first ? w * loss : acc + w * loss,
+# the step flag reset by the first micro-batch only) and its backward msu_dynloss_bwd3 (seed x w):
+# the weight is a launch argument, the window adds no ATen launch.  None: the plain forms.
+_loss_window = [None, 1.0, True, False]  # [acc, w, first, used by a loss launch since registered]
+
+
+def set_loss_window(acc, w=1.0, first=True):
+    """Register (or clear, ``set_loss_window(None)``) the window-loss accumulator (one f32) for the
+    DynamicLoss forward, with this micro-batch's weight ``w`` (B_i / n, a float that is exact in
+    f32) and whether it opens the window."""
+    _loss_window[0] = acc
+    _loss_window[1] = float(w)
+    _loss_window[2] = bool(first)
+    _loss_window[3] = False
+
+
+def loss_window_used():
+    """Whether a DynamicLoss launch folded its loss into the registered accumulator."""
+    return _loss_window[3]
+
+
+def _window_for(logits):
+    acc = _loss_window[0]
+    return _loss_window if acc is not None and acc.device == logits.device else None
+
+
 def _dynloss_impl(logits, target, alpha, beta, mix):
     _need_cuda(logits, target)
     logits = logits.contiguous()
@@ -1959,10 +1986,20 @@ def _dynloss_impl(logits, target, alpha, beta, mix):
     out = torch.empty((), device=logits.device, dtype=torch.float32)
     coef = torch.empty(B * 4 + 1, device=logits.device, dtype=torch.float32)
     zero = _step_flag[0] if _step_flag[0] is not None and _step_flag[0].device == logits.device else None
-    if zero is not None:
+    win = _window_for(logits)
+    if win is None:
+        if zero is not None:
+            _step_flag[1] = True
+        _lib.call("msu_dynloss_fwd3", _dt(logits), _p(logits), _p(target), B, N, alpha, beta, mix,
+                  _p(part), nblk, _p(out), coef.data_ptr() + 16 * B, _p(coef), _p(zero), _s(logits))
+        return out, coef
+    acc, w, first, _ = win
+    if zero is not None and first:
         _step_flag[1] = True
-    _lib.call("msu_dynloss_fwd3", _dt(logits), _p(logits), _p(target), B, N, alpha, beta, mix,
-              _p(part), nblk, _p(out), coef.data_ptr() + 16 * B, _p(coef), _p(zero), _s(logits))
+    _lib.call("msu_dynloss_fwd4", _dt(logits), _p(logits), _p(target), B, N, alpha, beta, mix,
+              _p(part), nblk, _p(out), coef.data_ptr() + 16 * B, _p(coef), _p(zero), _p(acc), w, int(first),
+              _s(logits))
+    win[3] = True
     return out, coef
 
 
@@ -1975,6 +2012,9 @@ def _dynloss_setup(ctx, inputs, output):
     out, coef = output
     ctx.save_for_backward(logits.contiguous(), _f32(target), coef, out)
     ctx.cfg = (alpha, beta, mix)
+    # inside an accumulation window the backward weights its seed by this micro-batch's share
+    win = _window_for(logits)
+    ctx.w = None if win is None else win[1]
     ctx.mark_non_differentiable(coef)
     ctx.set_materialize_grads(False)
 
@@ -1988,8 +2028,12 @@ def _dynloss_backward(ctx, g, _gc):
     N = logits[0].numel()
     g = _f32(g.reshape(1))
     dl = torch.empty(logits.shape, device=logits.device, dtype=torch.float32)
-    _lib.call("msu_dynloss_bwd2", _dt(logits), _p(logits), _p(target), _p(coef), coef.data_ptr() + 16 * B,
-              _p(g), B, N, alpha, beta, mix, _p(dl), _s(logits))
+    if ctx.w is None:
+        _lib.call("msu_dynloss_bwd2", _dt(logits), _p(logits), _p(target), _p(coef), coef.data_ptr() + 16 * B,
+                  _p(g), B, N, alpha, beta, mix, _p(dl), _s(logits))
+    else:
+        _lib.call("msu_dynloss_bwd3", _dt(logits), _p(logits), _p(target), _p(coef), coef.data_ptr() + 16 * B,
+                  _p(g), ctx.w, B, N, alpha, beta, mix, _p(dl), _s(logits))
     return dl.to(logits.dtype), None, None, None, None
 
 

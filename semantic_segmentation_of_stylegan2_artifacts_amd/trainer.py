@@ -20,6 +20,10 @@ Here:
 * AdamW = one fused HIP launch per group over the flat buffer, lr / step read from device
   memory, skipped (GradScaler semantics) when a gradient is non-finite; ``ema_decay`` adds an
   exponential moving average of the weights to that same launch, ``ema_scope()`` evaluates on it;
+* ``accum_steps=k`` (the reference's ``TRAIN.ACCUMULATION_STEPS``): ``step()`` cuts its batch into k
+  micro-batches whose backwards add into the flat gradients, each weighted by its share of the
+  batch in the loss kernels' seed; the check, the loss-scale update, AdamW and the all-reduce run
+  once per window;
 * after four eager steps the device side of the step is captured into a HIP graph and
   replayed (``Trainer.step``) when the eager step is launch-bound: the host then issues one
   launch per step;
@@ -198,6 +202,10 @@ class GradBucketer:
         # process group's watchdog as eager work; the watchdog's query of its event (recorded
         # in the capturing stream) then aborted the process (hipErrorCapturedEvent, r04f)
         self.capturing = False
+        # set by the Trainer for every micro-batch of an accumulation window but the last: a held
+        # backward neither counts accumulations nor launches, so the window's one all-reduce (of
+        # the summed gradient) belongs to its last backward, which counts like a plain step's
+        self.hold = False
         self.expected = None    # accumulations per bucket, learned on the first step
         self.pending = [0] * len(self.buckets)
         self.launched = [False] * len(self.buckets)
@@ -255,6 +263,8 @@ class GradBucketer:
             self.works.append((b,) + self._reduce(b, g, s, e))
 
     def _hook(self, p):
+        if self.hold:
+            return
         b = self.param_bucket[id(p)]
         self.pending[b] += 1
         if self.expected is not None and self.pending[b] == self.expected[b] and not self.capturing:
@@ -362,6 +372,25 @@ def ema_rule(ema, p, decay):
         return p - (p - e) * (np.float32(1.0) - w)
 
 
+def accum_split(n, k):
+    """The micro-batches of a gradient-accumulation window of ``n`` samples cut ``k`` ways:
+    ``[(start, stop, w)]`` by ``torch.tensor_split``'s rule (the first ``n % k`` pieces hold
+    ceil(n / k) samples, the rest floor(n / k)), ``w = float32(B_i / n)`` the piece's share of the
+    window's per-sample mean.  Each share rounds once, so the shares sum to 1 within k * 2^-24."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"accum_steps must be an int >= 1, got {k!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or n < k:
+        raise ValueError(f"a window of {n!r} samples cannot be cut into {k} micro-batches")
+    base, extra = divmod(n, k)
+    out, start = [], 0
+    for i in range(k):
+        size = base + (1 if i < extra else 0)
+        w = torch.tensor(size / n, dtype=torch.float64).to(torch.float32).item()
+        out.append((start, start + size, w))
+        start += size
+    return out
+
+
 def reseed(seed, rank=0):
     """Per-rank randomness for data parallelism: the model is built from the shared seed
     (identical initial weights on every rank), then every rank draws its own drop-path and
@@ -401,8 +430,13 @@ class Trainer:
     def __init__(self, model, config, device, lr=None, amp_dtype=torch.bfloat16, bucket_mb=32,
                  world_size=1, process_group=None, rank=0, seed=None, skip_nonfinite=True, use_graph=None,
                  graph_warmup=4, grad_wire_dtype=None, always_reduce=False, loss_scale=None, init_scale=65536.0,
-                 growth_interval=2000, max_grad_norm=None, ema_decay=None):
+                 growth_interval=2000, max_grad_norm=None, ema_decay=None, accum_steps=None):
         self.model = model
+        # accum_steps: None (config.TRAIN.ACCUMULATION_STEPS, 1 when the key is absent) or an int
+        # >= 1: step() cuts its batch into that many micro-batches and takes one optimizer step on
+        # their summed gradients (see step()); 1 is the plain step, launch for launch
+        self.accum_steps = self._check_accum_steps(
+            int(getattr(config.TRAIN, "ACCUMULATION_STEPS", 1)) if accum_steps is None else accum_steps)
         # ema_decay: None (no moving average: nothing allocated, nothing launched) or a float in
         # [0, 1): every applied AdamW step also moves a flat f32 average of the weights,
         # ema.lerp_(p, 1 - decay), in the optimizer's own pass (timm ModelEmaV2's rule and start);
@@ -477,6 +511,11 @@ class Trainer:
         self.skip_nonfinite = skip_nonfinite
         self.found_inf = torch.zeros(1, device=device, dtype=torch.float32)
         self._one = torch.ones((), device=device, dtype=torch.float32)
+        # the window's weighted-mean loss, folded together by the loss kernel of each micro-batch
+        # (persistent: the window stays capturable); micro_losses: the last window's per-micro-batch
+        # losses (device tensors, a readout)
+        self._window_loss = torch.zeros((), device=device, dtype=torch.float32) if self.accum_steps > 1 else None
+        self.micro_losses = []
         # the device-side loss scale: backward's seed, updated inside the step (replayable);
         # inv_out = inv_world / scale of the step in flight, what AdamW unscales by
         self.scale = self.growth_tracker = self.inv_out = None
@@ -547,6 +586,12 @@ class Trainer:
     def lr(self, value):
         self._lr = float(value)
         self.hyper[0:1].fill_(self._lr)
+
+    @staticmethod
+    def _check_accum_steps(value):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError(f"accum_steps must be None or an int >= 1, got {value!r}")
+        return value
 
     @staticmethod
     def _check_max_grad_norm(value):
@@ -801,9 +846,31 @@ class Trainer:
         refresh -- is
         captured once into a HIP graph and replayed: one launch per step instead of ~1300.
         Inputs are copied into the graph's static buffers; dropout keeps drawing fresh masks
-        (device-side seed counter, drop-path pools redrawn inside the graph)."""
+        (device-side seed counter, drop-path pools redrawn inside the graph).
+
+        ``accum_steps = k > 1``: the call is still ONE optimizer step, and its batch of ``n``
+        samples is the whole accumulation window.  It is cut into k micro-batches (views, by
+        ``accum_split``: ``torch.tensor_split``'s sizes); each runs forward and backward with the
+        seed weighted by ``w_i = B_i / n``, the backward kernels add into the flat gradients, and
+        the non-finite check, the loss-scale update, the clip factor, AdamW, the EMA and the shadow
+        refresh run once, after the last backward -- on the gradient of ``sum(w_i * loss_i)``,
+        which is DynamicLoss of the whole batch (a per-sample mean) and the loss returned
+        (unscaled).  So ``step_count``, ``optimizer_steps()``, ``skipped_steps()``, ``lr`` and the
+        EMA count windows, ``grad_norm()`` is the norm of the window-mean gradient, an overflow in
+        any micro-batch skips the whole window and backs the loss scale off once (GradScaler with
+        accumulation: unscale and check at the boundary), and data parallelism all-reduces the
+        summed gradient once per window.  ``n < k`` raises ValueError; a short last batch of an
+        epoch just has smaller micro-batches.  The whole window is captured as one graph (static
+        buffers of n samples; a window of another shape runs eagerly) in which every micro-batch
+        draws its own dropout and drop-path masks.  One difference to the whole batch: DynamicLoss
+        binarises its targets iff ``target.max() > 1``, decided over the batch it is given, which
+        is now each micro-batch -- identical for labels in {0, 1} or in {0, 255}.  A ``loss_fn``
+        that is not DynamicLoss gets its seed scaled and its losses summed by torch ops instead of
+        the fused loss forms (``msu_dynloss_fwd4`` / ``_bwd3``)."""
         if self._in_ema_scope:
             raise RuntimeError("step() inside ema_scope(): the weights and their EMA are swapped")
+        if self.accum_steps > 1:
+            accum_split(int(images.shape[0]), self.accum_steps)  # n < k: refused before any launch
         if not self.model.training:  # Module.train() walks all ~400 modules: ~1 ms of host time
             self.model.train()
         if self.graph_mode == "auto" and self.step_count >= self.graph_warmup and self._graph is None:
@@ -820,6 +887,76 @@ class Trainer:
     # ------------------------------------------------------------------ eager / captured body
     def _device_step(self, images, labels):
         """Everything the step enqueues on the GPU (the body that is captured)."""
+        if self.accum_steps > 1:
+            loss = self._window_backward(images, labels)
+        else:
+            loss = self._plain_backward(images, labels)
+        self._optimizer_tail()
+        return loss
+
+    def _window_backward(self, images, labels):
+        """Forward and backward of every micro-batch of an accumulation window: the backward kernels
+        add into the flat f32 gradients, so after the last one they hold the gradient of the
+        window's weighted-mean loss, which is returned (the persistent window-loss buffer)."""
+        red = self.reducer
+        if red is not None and torch.device(self.device).type == "cuda":
+            red.main_stream = torch.cuda.current_stream(self.device)
+        parts = accum_split(int(images.shape[0]), self.accum_steps)
+        # the fused forms need the project's own loss: another loss_fn gets its seed scaled and its
+        # loss summed with torch ops (as it gets the non-finite flag reset by a fill)
+        native = type(self.loss_fn) is DynamicLoss
+        seed = self._one if self.scale is None else self._seed
+        self.micro_losses = []
+        try:
+            for i, (a, b, w) in enumerate(parts):
+                last = i == len(parts) - 1
+                if self.use_graph:
+                    self.dev_seed.add_(1)  # every micro-batch draws its own dropout / drop-path masks
+                    model_parts.refresh_drop_pools()
+                if red is not None:
+                    red.hold = not last
+                ops.set_grad_ready_callback(red._hook if red is not None and last else None)
+                # msu_dynloss_fwd4 resets the non-finite flag from the first micro-batch only
+                ops.set_step_flag(self.found_inf)
+                if native:
+                    ops.set_loss_window(self._window_loss, w, i == 0)
+                try:
+                    loss = self.forward_loss(images[a:b], labels[a:b])
+                    if i == 0:
+                        self._flag_reset_by_loss = ops.step_flag_reset()
+                    fused = native and ops.loss_window_used()
+                finally:
+                    ops.set_step_flag(None)
+                    ops.set_loss_window(None)
+                self.micro_losses.append(loss.detach())
+                if fused:
+                    # the weight is msu_dynloss_bwd3's launch argument: under a loss scale the seed
+                    # stays the device scale itself, the captured window holds no host scalar
+                    loss.backward(seed)
+                else:
+                    if i == 0:
+                        torch.mul(loss.detach(), w, out=self._window_loss)
+                    else:
+                        self._window_loss.add_(loss.detach(), alpha=w)
+                    loss.backward(seed * w)
+                if not last:
+                    ops.join_side_streams()
+        except BaseException:
+            # no window state survives a step() call: the finished micro-batches' gradients must
+            # not join the next window's (a failed capture executed nothing: nothing to reset)
+            if torch.device(self.device).type != "cuda" or not torch.cuda.is_current_stream_capturing():
+                for g in self.groups:
+                    g.grad.zero_()
+            raise
+        finally:
+            if red is not None:
+                red.hold = False
+        if red is not None:
+            red.finish()  # one all-reduce of the summed gradient per window
+        ops.join_side_streams()
+        return self._window_loss
+
+    def _plain_backward(self, images, labels):
         if self.use_graph:
             self.dev_seed.add_(1)  # new attention-dropout masks per step / replay
             model_parts.refresh_drop_pools()
@@ -841,6 +978,11 @@ class Trainer:
         if self.reducer is not None:
             self.reducer.finish()
         ops.join_side_streams()  # weight gradients issued on the side stream
+        return loss.detach()
+
+    def _optimizer_tail(self):
+        """Once per step, after the (last) backward: the non-finite check, the loss-scale update,
+        the clip factor, AdamW with the gradient reset, the shadow refresh."""
         inv = self.inv_world if self.world_size > 1 else None
         amp16 = self.amp16
         if amp16:
@@ -886,7 +1028,6 @@ class Trainer:
                            shadow=g.shadow if amp16 else None, zero_grad=True, **ema)
             if amp16:  # keeps evaluation between steps on the updated weights
                 g.transpose_shadow()
-        return loss.detach()
 
     GRAPH_HOST_FRACTION = 0.9
 
@@ -923,7 +1064,8 @@ class Trainer:
         # the next step's refresh is skipped; a write through a parameter in between bumps its
         # version and the Linear ops cast that weight themselves (ops._shadow)
         self._shadow_fresh = self.amp16
-        return loss
+        # a window returns its persistent loss buffer: hand out a copy the next window leaves alone
+        return loss.clone() if self.accum_steps > 1 else loss
 
     def _param_versions(self):
         return sum(p._version for g in self.groups for p in g.params)
@@ -994,6 +1136,7 @@ class Trainer:
         self._graph = graph
         self._graph_loss_fn = self.loss_fn
         self._sloss = loss
+        self._smicro = list(self.micro_losses)  # the captured window's per-micro-batch losses
         self._versions = self._param_versions()
 
     def _replay(self, images, labels):
@@ -1013,6 +1156,7 @@ class Trainer:
         self._sx.copy_(images)
         self._sy.copy_(labels)
         self._graph.replay()
+        self.micro_losses = self._smicro
         self.step_count += 1
         return self._sloss.clone()
 
