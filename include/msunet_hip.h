@@ -377,6 +377,21 @@ int msu_metrics_nblk(long N);
 int msu_seg_metrics(int dtype, const void* logits, const float* label, int B, long N, float threshold,
                     float* part, int nblk, double* out, void* stream);
 
+/* Threshold sweep of the binary counts in one pass: p and g exactly as msu_seg_metrics forms them,
+ * thresholds [K] f32 on the device, strictly ascending (the caller checks), 1 <= K <=
+ * msu_seg_sweep_max_k() (1024).  hist [B][2][K + 1] int64 on the device, fully overwritten:
+ * hist[b][g][j] = pixels of image b in class g whose p exceeds exactly j thresholds (t_0 ..
+ * t_{j-1} < p, strict: a tie is not positive; a NaN logit lands in bin 0).  The tp / fp / fn / tn
+ * of threshold k are suffix sums of the rows (validation.sweep_counts) and equal
+ * msu_seg_metrics' at threshold t_k.  Per-block u32 histograms, flushed by 64-bit integer atomics
+ * after an in-stream clear: no scratch, no host sync, capturable, bitwise reproducible.  -2
+ * before any launch: K outside 1..max, B outside 1..65535, N outside 1..msu_seg_sweep_max_n()
+ * (2^41: beyond it a block's u32 bins could wrap), an unknown dtype, a null pointer. */
+int msu_seg_sweep_max_k();
+long msu_seg_sweep_max_n();
+int msu_seg_sweep(int dtype, const void* logits, const float* label, int B, long N, const float* thresholds,
+                  int K, long long* hist, void* stream);
+
 /* Test-split evaluation with prediction maps (test.py: calculate_metrics and
  * create_bin_heat_mask_from_list; scripts/map_generator.py save_color_heatmap :23-50,
  * overlay_mask_on_image :108-141) in one pass: logits [B, 1, H, W] (f32 / bf16 / f16), image

@@ -103,6 +103,9 @@ SIGNATURES = {
     "msu_nt_gemm_cat": (I, [I, P, P, I, P, P, P, L, I, I, P]),
     "msu_metrics_nblk": (I, [L]),
     "msu_seg_metrics": (I, [I, P, P, I, L, F, P, I, P, P]),
+    "msu_seg_sweep_max_k": (I, []),
+    "msu_seg_sweep_max_n": (L, []),
+    "msu_seg_sweep": (I, [I, P, P, I, L, P, I, P, P]),
     "msu_augment_batch": (I, [P, P, P, P, P, P, I, I, I, P]),
     "msu_augment_gather": (I, [P, P, P, I, P, P, P, P, I, I, I, P]),
     "msu_pred_maps_nblk": (I, [I, I]),

@@ -10,8 +10,12 @@ the BCE sum and the finished byte images; only ``[B, 12]`` doubles and bytes rea
 
     python -m semantic_segmentation_of_stylegan2_artifacts_amd.predict --cfg FILE \\
         --check_point_dir DIR --out_dir DIR [--batch_size N] [--no_labels] [--ema] [--cache]
+        [--sweep N | --sweep_thresholds a,b,c] [--select KEY[:MAX_FPR]]
 
 (``--ema``: the averaged weights a checkpoint saved with ``ema_state=`` holds under ``"model_ema"``.)
+``--sweep`` / ``--sweep_thresholds``: the binary metrics at every threshold of a list from the same
+forwards (``validation.threshold_histogram``), written to ``threshold_sweep.csv`` and
+``summary.sweep``; ``--select`` adds the chosen operating point (``validation.select_threshold``).
 
 Not ported: the matplotlib figure with a colour bar that ``save_color_heatmap`` draws around
 the overlay (``{case}_heatmap.png`` holds the overlay array itself), tensorboard, tqdm, csv.
@@ -19,6 +23,7 @@ the overlay (``{case}_heatmap.png`` holds the overlay array itself), tensorboard
 the outline here is the two-pixel band along every edge of the mask, holes included.
 """
 import argparse
+import csv
 import json
 import math
 import os
@@ -102,7 +107,7 @@ def _loss_cfg(loss_cfg):
 
 
 @torch.no_grad()
-def test_split(model, batches, loss_cfg, *, threshold=0.5, amp_dtype=torch.bfloat16, keep_maps=True):
+def test_split(model, batches, loss_cfg, *, threshold=0.5, amp_dtype=torch.bfloat16, keep_maps=True, sweep=None):
     """Run ``model`` in eval mode over the test split and return a ``TestResult``.
 
     ``batches`` yields ``(images, labels, case_names)``: images f32 [B, 3, H, W] in [0, 1] on
@@ -114,10 +119,16 @@ def test_split(model, batches, loss_cfg, *, threshold=0.5, amp_dtype=torch.bfloa
     False renders nothing.
 
     Per-image rows are ``validation.metrics_from_sums`` plus ``val_loss`` and ``case_name``
-    (unlabelled: ``case_name`` only); the summary is ``summarize_test`` (None unlabelled)."""
+    (unlabelled: ``case_name`` only); the summary is ``summarize_test`` (None unlabelled).
+    ``sweep``: a threshold sequence; the logits of every labelled batch then also go through
+    ``validation.threshold_histogram`` and the summary gains ``"sweep"``
+    (``validation.summarize_sweep``); the maps and every other field stay at ``threshold``."""
     alpha, beta, mix = _loss_cfg(loss_cfg)
+    if sweep is not None:
+        sweep = [float(t) for t in sweep]
+        validation.check_thresholds(sweep)
     model.eval()
-    per_image, output_list = [], []
+    per_image, output_list, hists = [], [], []
     count = 0
     for batch in batches:
         images, labels = batch[0], batch[1]
@@ -131,6 +142,8 @@ def test_split(model, batches, loss_cfg, *, threshold=0.5, amp_dtype=torch.bfloa
             logits = model(images)
         if logits.shape[1] != 1:
             raise ValueError(f"Binary task expected 1 logit channel, got {logits.shape[1]}")
+        if sweep is not None and labels is not None:
+            hists.append(validation.threshold_histogram(logits, labels, sweep).numpy())
         want = (("sums",) if labels is not None else ()) + \
                (("heat", "mask", "heat_rgb", "mask_rgb") if keep_maps else ())
         if not want:
@@ -166,6 +179,8 @@ def test_split(model, batches, loss_cfg, *, threshold=0.5, amp_dtype=torch.bfloa
     if len(labelled) != len(per_image):
         raise ValueError("labelled and unlabelled batches cannot be mixed in one split")
     summary = summarize_test(per_image)
+    if sweep is not None:
+        summary["sweep"] = validation.summarize_sweep(sweep, validation.sweep_counts(np.concatenate(hists)))
     return TestResult(summary["soft_dice"], output_list, summary["score"], summary["mean_fpr"], per_image, summary)
 
 
@@ -241,6 +256,28 @@ def dataset_batches(dataset, batch_size, device, cache=None):
         yield x, y, [dataset.sample_list[i].strip("\n") for i in idx]
 
 
+SWEEP_COLUMNS = validation.BINARY_KEYS + ("mean_fpr", "accuracy_all", "bin_score")
+
+
+def write_sweep_csv(path, sweep):
+    """One row per threshold of a ``validation.summarize_sweep`` dict: the per-threshold means and
+    the pooled pixel-level tpr / fpr / precision (empty cells for NaN)."""
+    pooled = ("tpr", "fpr", "precision")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(("threshold",) + SWEEP_COLUMNS + tuple("pooled_" + k for k in pooled))
+        for k, t in enumerate(sweep["thresholds"]):
+            row = [sweep[c][k] for c in SWEEP_COLUMNS] + [sweep["pooled"][c][k] for c in pooled]
+            w.writerow([repr(t)] + ["" if math.isnan(v) else repr(v) for v in row])
+
+
+def _parse_select(text):
+    key, _, bound = text.partition(":")
+    if key not in SWEEP_COLUMNS:
+        raise ValueError(f"--select: unknown key {key!r} (known: {', '.join(SWEEP_COLUMNS)})")
+    return key, (float(bound) if bound else None)
+
+
 def _jsonable(v):
     if isinstance(v, dict):
         return {k: _jsonable(x) for k, x in v.items()}
@@ -270,7 +307,30 @@ def main(argv=None):
     parser.add_argument("--cache", action="store_true",
                         help="keep the decoded split on the device (DeviceSampleCache, 4 B / pixel): the path "
                              "a training loop's per-epoch validation takes; one pass here decodes as much")
+    parser.add_argument("--sweep", type=int, default=None, metavar="N",
+                        help="also report the binary metrics at the N thresholds k / (N + 1)")
+    parser.add_argument("--sweep_thresholds", type=str, default=None, metavar="a,b,c",
+                        help="as --sweep with an explicit ascending threshold list")
+    parser.add_argument("--select", type=str, default=None, metavar="KEY[:MAX_FPR]",
+                        help="with a sweep: write the threshold with the largest KEY (e.g. bin_dice) among those "
+                             "with mean FPR <= MAX_FPR to metrics.json as selected_threshold")
     args = parser.parse_args(argv)
+    sweep = select = None
+    if args.sweep is not None and args.sweep_thresholds is not None:
+        parser.error("--sweep and --sweep_thresholds exclude each other")
+    if args.sweep is not None:
+        sweep = validation.default_thresholds(args.sweep)
+    elif args.sweep_thresholds is not None:
+        sweep = [float(t) for t in args.sweep_thresholds.split(",") if t.strip()]
+    if sweep is not None and args.no_labels:
+        parser.error("a threshold sweep needs labels")
+    if args.select is not None:
+        if sweep is None:
+            parser.error("--select needs --sweep or --sweep_thresholds")
+        try:
+            select = _parse_select(args.select)
+        except ValueError as e:
+            parser.error(str(e))
     config = load_config(args.cfg)
     if not torch.cuda.is_available():
         raise RuntimeError("predict needs a HIP device (no CPU fallback)")
@@ -302,9 +362,15 @@ def main(argv=None):
                      (config.TRAIN.TVERSKY_LOSS_ALPHA, config.TRAIN.TVERSKY_LOSS_BETA,
                       config.TRAIN.LOSS_TVERSKY_BCE_MIX),
                      threshold=config.TRAIN.SIG_THRESHOLD, amp_dtype=torch.float16,
-                     keep_maps=lambda name, maps: save_maps(name, maps, pred_dir))
+                     keep_maps=lambda name, maps: save_maps(name, maps, pred_dir), sweep=sweep)
+    report = {"date": timestamp_str, "summary": res.summary, "per_image": res.per_image}
+    if sweep is not None:
+        write_sweep_csv(os.path.join(output_dir, "threshold_sweep.csv"), res.summary["sweep"])
+    if select is not None:
+        report["selected_threshold"] = validation.select_threshold(res.summary["sweep"], *select)
+        report["selection"] = {"key": select[0], "max_fpr": select[1]}
     with open(os.path.join(output_dir, "metrics.json"), "w") as f:
-        json.dump(_jsonable({"date": timestamp_str, "summary": res.summary, "per_image": res.per_image}), f, indent=1)
+        json.dump(_jsonable(report), f, indent=1)
     if res.summary is not None:
         print(f"mean_dice_test: {res.mean_soft_dice:.6f}, Score: {res.score:.6f}, FPR: {res.mean_fpr:.6f}")
     print(timestamp_str, file=sys.stdout)
